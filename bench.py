@@ -7,6 +7,15 @@ checks a FRESH batch of 1M states (a sampler streaming new samples): 16 resident
 (400 MB, larger than the 256 MB Infinity Cache) are rotated, so the timed kernels stream
 from HBM.  Inputs are resident in HBM before the timed region.
 
+A plain run (`--gpus 1 --steps K --warmup W`) does only that: set-up, W warm-up steps, the
+K timed steps, the JSON line (ms_per_step = the timed region's wall time / K).  With
+`--dump-outputs DIR` it also writes what the last timed step computed -- the 1,048,576
+validity flags a caller of World.check_states receives for resident batch (K - 1) % 16, as
+float32 0/1 -- to DIR/valid.npy (DIR/valid_rank<r>.npy at N > 1); the inputs are
+counter-based and seeded, so two runs with the same arguments check the same states.
+Everything below the next paragraph (the full-plan leg, the side measurements, the CPU
+baseline and the parity against the oracle) runs only with `--full`.
+
 Multi-GPU: one process per GPU (torchrun, or `--gpus N` spawning its own ranks); every
 rank checks its own stream of states against its own copy of the world (independent
 samplers, no data-path collective: "scaling": "weak"); ranks synchronise with a barrier
@@ -81,9 +90,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)  # ~17 ms timed: host hiccups amortised
     ap.add_argument("--warmup", type=int, default=200)  # ~2 ms of GPU work: clocks settle
-    ap.add_argument("--no-side", action="store_true", help="skip the side measurements (C3, C5)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline")
-    ap.add_argument("--no-plan", action="store_true", help="skip the full-plan (C4) leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the full-plan (C4) leg, the side measurements (C1, C3, C5), the CPU baseline and "
+                         "the parity against the oracle; without it only the headline's timed steps run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy")
+    ap.add_argument("--no-side", action="store_true", help="with --full: skip the side measurements (C3, C5)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline and the parity")
+    ap.add_argument("--no-plan", action="store_true", help="with --full: skip the full-plan (C4) leg")
     ap.add_argument("--plan-reps", type=int, default=20)  # the seed changes per call: ~1 in 6 takes the slower symmetrised search
     ap.add_argument("--host-loop", action="store_true",
                     help="launch the timed steps from a host loop instead of replaying a captured HIP graph")
@@ -97,6 +111,10 @@ def main():
     ap.add_argument("--parity-flip-rank", type=int, default=-1,
                     help="with --launcher-check: this rank reports one C2 flag mismatch (parity reduction test)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:  # a plain run: the headline's timed steps only
+        args.no_side = args.no_cpu = args.no_plan = True
 
     from eppamd.dist import LegFailed, env, make_group, spawn_ranks
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -219,12 +237,20 @@ def run(args, ws, rank, local, out_stream):
     if graph is not None:
         capi.check(L.epp_graph_destroy(graph))
     achieved = BYTES_PER_STATE * N_STATES / (kms * 1e-3) / 1e9
-    n_valid = int(d_valid.download(np.uint8, N_STATES).sum())
+    # what the last timed step wrote: the validity flags of resident batch (K - 1) % 16
+    last_flags = d_valid.download(np.uint8, N_STATES)
+    n_valid = int(last_flags.sum())
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "valid.npy" if ws == 1 else f"valid_rank{rank}.npy"),
+                last_flags.astype(np.float32))
     # parity: the flags of resident batch 0 (the cpu_baseline leg checks the same batch on
     # the oracle and counts the mismatches)
-    step(0)
-    capi.check(L.epp_stream_sync(stream))
-    c2_flags = d_valid.download(np.uint8, N_STATES)
+    c2_flags = None
+    if not args.no_cpu:
+        step(0)
+        capi.check(L.epp_stream_sync(stream))
+        c2_flags = d_valid.download(np.uint8, N_STATES)
 
     traffic, traffic_src = committed_traffic()
 
@@ -257,6 +283,7 @@ def run(args, ws, rank, local, out_stream):
             "n_gpus": ws,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": bool(args.full),
             "ms_per_step": elapsed / args.steps * 1e3,
             "higher_is_better": True,
             "scaling": "weak",

@@ -1,8 +1,8 @@
 """Summarise a gpu_check.sh session into profiles/<tag>_*.{csv,json} (committed).
 
   <tag>_kernel_stats.csv   rocprofv3 --kernel-trace --stats summary of the bench headline
-                           (`python3 bench.py --no-cpu --no-plan --no-side`: one launch shape)
-  <tag>_kernel_stats_full.csv  the same over the whole bench (`--no-cpu`: plan + side legs)
+                           (`python3 bench.py`, a plain run: one launch shape)
+  <tag>_kernel_stats_full.csv  the same over the whole bench (`--full --no-cpu`: plan + side legs)
   <tag>_traffic.json       HBM bytes per k_states launch from the FETCH_SIZE / WRITE_SIZE passes,
                            corrected as MI355X_MICROARCH.md prescribes: FETCH_SIZE counts half the
                            bytes of a wide (16 B/lane) streaming read on gfx950 -> x2; both in KB.

@@ -38,3 +38,12 @@ def test_cpu_bench_reads_bench_input(cfg, geom):
     wp2[wi, :2] = [g[gate, 0] + d[0], g[gate, 1] + d[1]]
     assert out["online_rows"] == len(O.generate_trajectory(wp2, 1.0, 2.0, 0.1, 0.0, bench.C5_V0, bench.C5_A0))
     assert out["c5_online_native"]["p50_us"] > 0 and np.isfinite(out["c5_refit_native"]["p99_us"])
+
+
+def test_bench_options():
+    """The plain run's options: --full and --dump-outputs exist, --steps must be positive."""
+    exe = [sys.executable, os.path.join(ROOT, "bench.py")]
+    r = subprocess.run(exe + ["--help"], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs DIR" in r.stdout, r.stdout
+    r = subprocess.run(exe + ["--steps", "0"], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr, r.stderr
