@@ -14,19 +14,20 @@
 
 namespace py = pybind11;
 
+static void read3(py::object o, double* out) {
+    if (o.is_none()) return;
+    auto a = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(o);
+    if (!a || a.size() != 3) throw std::invalid_argument("initial velocity/acceleration must have 3 entries");
+    for (int i = 0; i < 3; ++i) out[i] = a.data()[i];
+}
+
 static py::array_t<double> generate_trajectory(py::array_t<double, py::array::c_style | py::array::forcecast> waypoints,
                                                double v_max, double a_max, double sampling_intervall,
                                                double start_time_offset, py::object initial_vel,
-                                               py::object initial_acc) {
+                                               py::object initial_acc, bool enforce_limits) {
     if (waypoints.ndim() != 2 || waypoints.shape(1) != 3)
         throw std::invalid_argument("waypoints must be an (n, 3) array");
     double v0[3] = {0, 0, 0}, a0[3] = {0, 0, 0};
-    auto read3 = [](py::object o, double* out) {
-        if (o.is_none()) return;
-        auto a = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(o);
-        if (!a || a.size() != 3) throw std::invalid_argument("initial velocity/acceleration must have 3 entries");
-        for (int i = 0; i < 3; ++i) out[i] = a.data()[i];
-    };
     read3(initial_vel, v0);
     read3(initial_acc, a0);
     double* rows = nullptr;
@@ -34,8 +35,14 @@ static py::array_t<double> generate_trajectory(py::array_t<double, py::array::c_
     epp_status rc;
     {
         py::gil_scoped_release release;
-        rc = epp_generate_trajectory_host(waypoints.data(), (int32_t)waypoints.shape(0), v_max, a_max,
-                                          sampling_intervall, start_time_offset, v0, a0, &rows, &n);
+        // enforceLimits: the fit time-scaled until its peak speed and acceleration are within
+        // v_max / a_max (Trajectory::scaleSegmentTimesToMeetConstraints, src/trajectory.cpp:385-429)
+        rc = enforce_limits
+                 ? epp_generate_trajectory_limited_host(waypoints.data(), (int32_t)waypoints.shape(0), v_max, a_max,
+                                                        sampling_intervall, start_time_offset, v0, a0, &rows, &n,
+                                                        nullptr)
+                 : epp_generate_trajectory_host(waypoints.data(), (int32_t)waypoints.shape(0), v_max, a_max,
+                                                sampling_intervall, start_time_offset, v0, a0, &rows, &n);
     }
     if (rc == EPP_ERR_INVALID_ARGUMENT) throw std::invalid_argument(epp_last_error());
     if (rc != EPP_OK) throw std::runtime_error(epp_last_error());
@@ -45,9 +52,59 @@ static py::array_t<double> generate_trajectory(py::array_t<double, py::array::c_
     return out;
 }
 
+// Trajectory::computeMaxVelocityAndAcceleration (src/trajectory.cpp:344-361) of the fit
+// generate_trajectory samples: (v_peak, a_peak).
+static py::tuple max_velocity_and_acceleration(py::array_t<double, py::array::c_style | py::array::forcecast> waypoints,
+                                               double v_max, double a_max, py::object initial_vel,
+                                               py::object initial_acc) {
+    if (waypoints.ndim() != 2 || waypoints.shape(1) != 3)
+        throw std::invalid_argument("waypoints must be an (n, 3) array");
+    const int32_t W = (int32_t)waypoints.shape(0);
+    if (W < 2) throw std::invalid_argument("At least two waypoints are required");
+    double va[6] = {0, 0, 0, 0, 0, 0};
+    read3(initial_vel, va);
+    read3(initial_acc, va + 3);
+    const int32_t M = W - 1, off[2] = {0, W};
+    // one device block: [wp (3 W) | v0 a0 (6) | T (M) | coeffs (30 M) | peaks (4) | offsets, statuses (int32 x 4)]
+    const size_t nd = (size_t)3 * W + 6 + (size_t)M * 31 + 4;
+    double peaks[4] = {0, 0, 0, 0};
+    int32_t st[2] = {0, 0};
+    void* buf = nullptr;
+    epp_status rc;
+    {
+        py::gil_scoped_release release;
+        rc = epp_malloc(&buf, nd * 8 + 16);
+        if (rc == EPP_OK) {
+            double* d_wp = static_cast<double*>(buf);
+            double* d_va = d_wp + 3 * W;
+            double* d_T = d_va + 6;
+            double* d_C = d_T + M;
+            double* d_pk = d_C + (size_t)M * 30;
+            int32_t* d_off = reinterpret_cast<int32_t*>(d_pk + 4);
+            int32_t* d_st = d_off + 2;
+            rc = epp_memcpy_h2d(d_wp, waypoints.data(), (size_t)W * 24, nullptr);
+            if (rc == EPP_OK) rc = epp_memcpy_h2d(d_va, va, sizeof(va), nullptr);
+            if (rc == EPP_OK) rc = epp_memcpy_h2d(d_off, off, sizeof(off), nullptr);
+            if (rc == EPP_OK)
+                rc = epp_minsnap_batch(d_wp, d_off, 1, v_max, a_max, d_va, d_va + 3, d_T, d_C, d_st, nullptr);
+            if (rc == EPP_OK) rc = epp_traj_peaks(d_T, d_C, d_off, 1, d_pk, d_st + 1, nullptr);
+            if (rc == EPP_OK) rc = epp_memcpy_d2h(peaks, d_pk, sizeof(peaks), nullptr);
+            if (rc == EPP_OK) rc = epp_memcpy_d2h(st, d_st, sizeof(st), nullptr);
+            epp_free(buf);
+        }
+    }
+    if (rc == EPP_ERR_INVALID_ARGUMENT) throw std::invalid_argument(epp_last_error());
+    if (rc != EPP_OK) throw std::runtime_error(epp_last_error());
+    if (st[0] == -2) throw std::runtime_error("Segment times need to be greater than zero");
+    if (st[0] != 0 || st[1] != 0) throw std::runtime_error("min-snap solve failed");
+    return py::make_tuple(peaks[0], peaks[2]);
+}
+
 PYBIND11_MODULE(polynomial_trajectory, m) {
     m.doc() = "MI355X min-snap trajectory generation (drop-in for poly_traj::generateTrajectory)";
     m.def("generate_trajectory", &generate_trajectory, py::arg("waypoints"), py::arg("v_max"), py::arg("a_max"),
           py::arg("sampling_intervall"), py::arg("startTimeOffset") = 0.0, py::arg("initialVel") = py::none(),
-          py::arg("initialAcc") = py::none());
+          py::arg("initialAcc") = py::none(), py::arg("enforceLimits") = false);
+    m.def("max_velocity_and_acceleration", &max_velocity_and_acceleration, py::arg("waypoints"), py::arg("v_max"),
+          py::arg("a_max"), py::arg("initialVel") = py::none(), py::arg("initialAcc") = py::none());
 }

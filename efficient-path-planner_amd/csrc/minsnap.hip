@@ -985,7 +985,7 @@ epp_status read_offsets(const int32_t* d_off, int n_tracks, hipStream_t s, const
 
 epp_status minsnap_batch(const double* wp, const int32_t* wp_offsets, int32_t n_tracks, double v_max, double a_max,
                          const double* v0, const double* a0, const double* times_in, double* seg_times, double* coeffs,
-                         int32_t* status, void* stream, const char* what) {
+                         int32_t* status, void* stream, const char* what, int known_m = -1) {
     if (n_tracks < 0 || (n_tracks > 0 && (!wp || !wp_offsets || !seg_times || !coeffs))) {
         set_error(std::string(what) + ": invalid argument");
         return EPP_ERR_INVALID_ARGUMENT;
@@ -996,7 +996,12 @@ epp_status minsnap_batch(const double* wp, const int32_t* wp_offsets, int32_t n_
     hipStream_t s = (hipStream_t)stream;
     int max_m = 0;
     int64_t total_m = 0;
-    if ((st = read_offsets(wp_offsets, n_tracks, s, what, &max_m, &total_m))) return st;
+    if (known_m >= 0) {  // (one track whose segment count the host caller knows)
+        max_m = std::max(1, known_m);
+        total_m = known_m;
+    } else if ((st = read_offsets(wp_offsets, n_tracks, s, what, &max_m, &total_m))) {
+        return st;
+    }
     constexpr int kB = 64;  // one wavefront per track: the batch is throughput-bound
     // one refinement step in every track's solve (solve_track): +50 % kernel time, 10-100x
     // the accuracy on short and mixed segments (scripts/minsnap_truth_probe.py, DESIGN.md
@@ -1096,6 +1101,55 @@ struct RefitCache {
             set_error(std::string("generateTrajectory: buffers: ") + hipGetErrorString(e));
             return EPP_ERR_HIP;
         }
+        return EPP_OK;
+    }
+};
+
+// Per-host-thread state of epp_generate_trajectory_limited_host: a stream and two pinned
+// host buffers (the track's inputs, times, coefficients and flags; the rows) that the three
+// kernels read and write directly.
+struct LimitedCache {
+    hipStream_t s = nullptr;
+    int dev = -1;
+    char* h_io = nullptr;
+    size_t io_cap = 0;
+    char* h_rows = nullptr;
+    size_t rows_cap = 0;
+    void release() {
+        if (s) (void)hipStreamSynchronize(s);
+        if (h_io) (void)hipHostFree(h_io);
+        if (h_rows) (void)hipHostFree(h_rows);
+        if (s) (void)hipStreamDestroy(s);
+        h_io = h_rows = nullptr;
+        s = nullptr;
+        io_cap = rows_cap = 0;
+    }
+    ~LimitedCache() { release(); }
+    epp_status stream_on_device() {
+        int d = 0;
+        (void)hipGetDevice(&d);
+        if (d != dev) release();
+        dev = d;
+        if (!s && hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) {
+            s = nullptr;
+            set_error("generateTrajectory: stream");
+            return EPP_ERR_HIP;
+        }
+        return EPP_OK;
+    }
+    epp_status grow(char*& p, size_t& cap, size_t need) {
+        if (need <= cap) return EPP_OK;
+        (void)hipStreamSynchronize(s);
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        cap = 0;
+        const hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&p), need, hipHostMallocDefault);
+        if (e != hipSuccess) {
+            p = nullptr;
+            set_error(std::string("generateTrajectory: buffers: ") + hipGetErrorString(e));
+            return EPP_ERR_HIP;
+        }
+        cap = need;
         return EPP_OK;
     }
 };
@@ -1414,6 +1468,113 @@ epp_status epp_generate_trajectory_times_host(const double* wp, int32_t n_wp, co
         return EPP_ERR_INVALID_ARGUMENT;
     }
     return generate_trajectory(wp, n_wp, seg_times, 0.0, 0.0, dt, t0, v0, a0, rows_out, n_rows);
+}
+
+// generateTrajectory followed by Trajectory::scaleSegmentTimesToMeetConstraints
+// (src/trajectory.cpp:385-429) before the sampling: three launches on the calling thread's
+// stream over pinned host buffers -- the batch fit (k_minsnap, one track), k_traj_scale,
+// then, after the host has run evaluateRange's sample recurrence on the SCALED times to
+// size the row buffer, k_sample_rows.
+epp_status epp_generate_trajectory_limited_host(const double* wp, int32_t n_wp, double v_max, double a_max, double dt,
+                                                double t0, const double v0[3], const double a0[3], double** rows_out,
+                                                int64_t* n_rows, double* scale_out) {
+    if (!rows_out || !n_rows || (n_wp > 0 && !wp)) {
+        set_error("generateTrajectory: invalid argument");
+        return EPP_ERR_INVALID_ARGUMENT;
+    }
+    *rows_out = nullptr;
+    *n_rows = 0;
+    if (n_wp < 2) {
+        set_error("At least two waypoints are required");  // trajectory_generator.cpp:24
+        return EPP_ERR_INVALID_ARGUMENT;
+    }
+    if (!(v_max > 0.0) || !(a_max > 0.0)) {
+        set_error("generateTrajectory: v_max and a_max must be greater than zero to enforce them");
+        return EPP_ERR_INVALID_ARGUMENT;
+    }
+    const int M = n_wp - 1;
+    for (int i = 0; i < M; ++i)
+        if (!(nfabian(wp + 3 * i, wp + 3 * (i + 1), v_max, a_max) > 0)) {  // CHECK_GT(segment_time, 0)  impl :297
+            set_error("Segment times need to be greater than zero");
+            return EPP_ERR_RUNTIME;
+        }
+    static thread_local LimitedCache c;
+    epp_status rc = c.stream_on_device();
+    if (rc) return rc;
+    const size_t nd = (size_t)3 * n_wp + 6 + (size_t)M * 31 + 2;  // doubles before the int32 words
+    if ((rc = c.grow(c.h_io, c.io_cap, nd * 8 + 16))) return rc;
+    double* h_wp = reinterpret_cast<double*>(c.h_io);
+    double* h_v0 = h_wp + 3 * n_wp;
+    double* h_a0 = h_v0 + 3;
+    double* h_T = h_a0 + 3;
+    double* h_C = h_T + M;
+    double* h_scale = h_C + (size_t)M * 30;
+    double* h_t0 = h_scale + 1;
+    int32_t* h_off = reinterpret_cast<int32_t*>(h_t0 + 1);
+    int32_t* h_st = h_off + 2;  // [fit, scale]
+    std::memcpy(h_wp, wp, (size_t)n_wp * 24);
+    for (int k = 0; k < 3; ++k) {
+        h_v0[k] = v0 ? v0[k] : 0.0;
+        h_a0[k] = a0 ? a0[k] : 0.0;
+    }
+    *h_scale = 1.0;
+    *h_t0 = t0;
+    h_off[0] = 0;
+    h_off[1] = n_wp;
+    h_st[0] = h_st[1] = -100;
+    if ((rc = minsnap_batch(h_wp, h_off, 1, v_max, a_max, h_v0, h_a0, nullptr, h_T, h_C, h_st, c.s,
+                            "generateTrajectory", M)))
+        return rc;
+    if ((rc = epp_traj_scale_to_limits(h_T, h_C, h_off, 1, v_max, a_max, h_scale, h_st + 1, c.s))) return rc;
+    hipError_t e = hipStreamSynchronize(c.s);
+    if (e != hipSuccess) {
+        set_error(std::string("generateTrajectory: ") + hipGetErrorString(e));
+        return EPP_ERR_HIP;
+    }
+    if (h_st[0] != 0 || h_st[1] != 0) {
+        set_error(h_st[0] == -2   ? "Segment times need to be greater than zero"
+                  : h_st[0] != 0  ? "min-snap solve failed"
+                  : h_st[1] == 1  ? "generateTrajectory: v_max / a_max not met after 20 rounds of time scaling"
+                                  : "generateTrajectory: the fit is not finite");
+        return EPP_ERR_RUNTIME;
+    }
+    int64_t R = 0;
+    if (dt > 0) {  // Trajectory::evaluateRange's recurrence on the scaled times (exact count)
+        RangeIter it;
+        it.init(h_T, M);
+        int sg;
+        double ti, ta;
+        while (it.next(sg, ti, ta)) {
+            ++R;
+            it.advance(dt);
+        }
+    }
+    double* rows = (double*)std::malloc((size_t)std::max<int64_t>(R, 1) * 80);
+    if (!rows) {
+        set_error("generateTrajectory: out of host memory");
+        return EPP_ERR_RUNTIME;
+    }
+    if (R) {
+        if ((rc = ensure_consts()) || (rc = c.grow(c.h_rows, c.rows_cap, (size_t)R * 80))) {
+            std::free(rows);
+            return rc;
+        }
+        const size_t shm = ((size_t)kNC + ((M + 1) & ~1) + 3 * kRowChunk + 2) * 8;
+        hipLaunchKernelGGL(k_sample_rows, dim3(1), dim3(kWave), shm, c.s, h_T, h_C, h_off, 1, dt, h_t0,
+                           (const int64_t*)nullptr, reinterpret_cast<double*>(c.h_rows), R);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(c.s);
+        if (e != hipSuccess) {
+            std::free(rows);
+            set_error(std::string("generateTrajectory: ") + hipGetErrorString(e));
+            return EPP_ERR_HIP;
+        }
+        std::memcpy(rows, c.h_rows, (size_t)R * 80);
+    }
+    if (scale_out) *scale_out = *h_scale;
+    *rows_out = rows;
+    *n_rows = R;
+    return EPP_OK;
 }
 
 #ifdef EPP_REFIT_TL

@@ -93,6 +93,11 @@ def lib() -> C.CDLL:
             "epp_minsnap_batch_times": (i32, [vp, vp, i32, vp, vp, vp, vp, vp, vp]),
             "epp_sample_count": (i32, [vp, vp, i32, dp, vp, vp]),
             "epp_sample_batch": (i32, [vp, vp, vp, i32, dp, vp, vp, vp, vp]),
+            "epp_traj_peaks": (i32, [vp, vp, vp, i32, vp, vp, vp]),
+            "epp_traj_scale_to_limits": (i32, [vp, vp, vp, i32, dp, dp, vp, vp, vp]),
+            "epp_generate_trajectory_limited_host": (i32, [vp, i32, dp, dp, dp, dp, vp, vp,
+                                                           C.POINTER(C.POINTER(C.c_double)), C.POINTER(i64),
+                                                           C.POINTER(C.c_double)]),
             "epp_check_and_generate_trajectory_host": (i32, [vp, vp, i64, dp, vp, vp, i32, dp, dp, dp, dp, vp, vp,
                                                                C.POINTER(C.POINTER(C.c_double)), C.POINTER(i64)]),
             "epp_generate_trajectory_host": (i32, [vp, i32, dp, dp, dp, dp, vp, vp,
@@ -148,6 +153,7 @@ EXPORTED = [
     "epp_comm_init_all", "epp_comm_destroy", "epp_comm_rank", "epp_comm_allgather_waypoints",
     "epp_comm_allreduce_f64", "epp_comm_barrier", "epp_comm_available", "epp_knn_ws_box", "epp_knn_grid_ws_box",
     "epp_comm_set_timeout", "epp_comm_abort", "epp_check_and_generate_trajectory_host",
+    "epp_traj_peaks", "epp_traj_scale_to_limits", "epp_generate_trajectory_limited_host",
 ]
 
 
@@ -397,6 +403,72 @@ def generate_trajectory(waypoints, v_max, a_max, dt, t0=0.0, v0=(0, 0, 0), a0=(0
     out = np.ctypeslib.as_array(rows, shape=(n.value * 10,)).copy().reshape(-1, 10)
     lib().epp_host_free(C.cast(rows, C.c_void_p))
     return out
+
+
+def _upload_tracks(Ts, Cs):
+    """The device layout of epp_minsnap_batch's outputs for lists of per-track segment times
+    and coefficients (a track of W waypoints has W - 1 segments; an empty entry stands for a
+    1-waypoint track)."""
+    Ts = [np.asarray(t, np.float64).ravel() for t in Ts]
+    nt = len(Ts)
+    off = np.zeros(nt + 1, np.int32)
+    off[1:] = np.cumsum([len(t) + 1 for t in Ts])
+    nseg = int(sum(len(t) for t in Ts))
+    T = np.concatenate(Ts + [np.zeros(0)])
+    Cf = np.concatenate([np.asarray(c, np.float64).reshape(-1, 3, 10) for c in Cs] + [np.zeros((0, 3, 10))])
+    assert len(Cf) == nseg
+    d_T, d_C = DeviceBuffer(8 * max(nseg, 1)), DeviceBuffer(240 * max(nseg, 1))
+    if nseg:
+        d_T.upload(T)
+        d_C.upload(Cf)
+    return d_T, d_C, DeviceBuffer.from_array(off), off, nseg
+
+
+def traj_peaks(Ts, Cs):
+    """epp_traj_peaks on the lists minsnap_batch returns: ((n, 4) array [v_peak, t_v, a_peak,
+    t_a], status array)."""
+    nt = len(Ts)
+    d_T, d_C, d_off, _, _ = _upload_tracks(Ts, Cs)
+    d_pk, d_st = DeviceBuffer(32 * nt), DeviceBuffer(4 * nt)
+    check(lib().epp_traj_peaks(d_T.ptr, d_C.ptr, d_off.ptr, nt, d_pk.ptr, d_st.ptr, None))
+    sync()
+    return d_pk.download(np.float64, 4 * nt).reshape(nt, 4), d_st.download(np.int32, nt)
+
+
+def scale_to_limits(Ts, Cs, v_max, a_max):
+    """epp_traj_scale_to_limits: (new seg_times list, new coeffs list, scale array, status array)."""
+    nt = len(Ts)
+    d_T, d_C, d_off, off, nseg = _upload_tracks(Ts, Cs)
+    d_sc, d_st = DeviceBuffer(8 * nt), DeviceBuffer(4 * nt)
+    check(lib().epp_traj_scale_to_limits(d_T.ptr, d_C.ptr, d_off.ptr, nt, float(v_max), float(a_max), d_sc.ptr,
+                                         d_st.ptr, None))
+    sync()
+    T = d_T.download(np.float64, nseg)
+    Cf = d_C.download(np.float64, nseg * 30).reshape(nseg, 3, 10)
+    Tn, Cn = [], []
+    for k in range(nt):
+        a, b = int(off[k]) - k, int(off[k + 1]) - k - 1
+        Tn.append(T[a:max(a, b)])
+        Cn.append(Cf[a:max(a, b)])
+    return Tn, Cn, d_sc.download(np.float64, nt), d_st.download(np.int32, nt)
+
+
+def generate_trajectory_limited(waypoints, v_max, a_max, dt, t0=0.0, v0=(0, 0, 0), a0=(0, 0, 0), return_scale=False):
+    """epp_generate_trajectory_limited_host: generate_trajectory with the fit time-scaled to
+    meet v_max / a_max (Trajectory::scaleSegmentTimesToMeetConstraints,
+    external/poly_traj/src/trajectory.cpp:385-429).  return_scale: (rows, scale)."""
+    wp = np.ascontiguousarray(np.asarray(waypoints, np.float64).reshape(-1, 3))
+    v0 = np.ascontiguousarray(v0, np.float64)
+    a0 = np.ascontiguousarray(a0, np.float64)
+    rows = C.POINTER(C.c_double)()
+    n = C.c_int64(0)
+    scale = C.c_double(1.0)
+    check(lib().epp_generate_trajectory_limited_host(_ptr(wp), len(wp), float(v_max), float(a_max), float(dt),
+                                                     float(t0), _ptr(v0), _ptr(a0), C.byref(rows), C.byref(n),
+                                                     C.byref(scale)))
+    out = np.ctypeslib.as_array(rows, shape=(n.value * 10,)).copy().reshape(-1, 10) if n.value else np.zeros((0, 10))
+    lib().epp_host_free(C.cast(rows, C.c_void_p))
+    return (out, scale.value) if return_scale else out
 
 
 def check_and_generate_trajectory(world: "World", check_xyz, min_distance, waypoints, v_max, a_max, dt, t0=0.0,

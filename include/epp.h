@@ -186,6 +186,35 @@ epp_status epp_sample_count(const double* seg_times, const int32_t* wp_offsets, 
 epp_status epp_sample_batch(const double* seg_times, const double* coeffs,
                             const int32_t* wp_offsets, int32_t n_tracks, double dt, const double* t0,
                             const int64_t* row_offsets, double* rows, void* stream);
+/* Trajectory::computeMaxVelocityAndAcceleration (external/poly_traj/src/trajectory.cpp:344-361,
+ * computeMinMaxMagnitude :191-227, over the per-segment magnitude extrema of
+ * external/poly_traj/src/segment.cpp:83-185), batched over tracks in the layout of
+ * epp_minsnap_batch.  peaks: n_tracks x 4 [v_peak, t_v, a_peak, t_a]: the maxima over the
+ * whole track of the Euclidean norm (x, y, z) of the first and second derivative, and
+ * where they occur, as time from the start of the track (the sum of the earlier segment
+ * times plus the time in the segment; equal maxima report the earliest).  The extrema are
+ * the segment ends and the roots of sum_d p_d^(k) p_d^(k+1), bracketed on 64 subintervals
+ * per segment and bisected (not the reference's Jenkins-Traub roots of the convolved
+ * polynomial): a subinterval holding two roots is not searched, so a bump of the magnitude
+ * narrower than 1/64 of its segment can be missed.  status (n_tracks, may be NULL): 0 ok;
+ * -1 fewer than one segment, a segment time <= 0 or non-finite input (the buffers of a
+ * track that epp_minsnap_batch failed): its peaks are NaN. */
+epp_status epp_traj_peaks(const double* seg_times, const double* coeffs, const int32_t* wp_offsets,
+                          int32_t n_tracks, double* peaks, int32_t* status, void* stream);
+/* Trajectory::scaleSegmentTimesToMeetConstraints (external/poly_traj/src/trajectory.cpp:385-429)
+ * per track, in place on seg_times and coeffs, the whole loop in one launch: at most 20
+ * rounds of [peaks as epp_traj_peaks; vv = v_peak / v_max, av = a_peak / a_max; done when
+ * both are <= 1 + 1e-3; else every segment time times s = max(1, vv, sqrt(av)) and every
+ * polynomial scaled in time with 1 / s (Polynomial::scalePolynomialInTime,
+ * external/poly_traj/src/polynomial.cpp:199-205)].  One factor for the whole track: the
+ * path keeps its shape, x_new(s t) = x_old(t).  scale: n_tracks, the product of the
+ * factors applied; a track within the limits comes back bit for bit with scale 1.0.
+ * status (n_tracks, may be NULL): 0 within the limits; 1 still outside after 20 rounds;
+ * -1 as epp_traj_peaks (the track is left untouched, scale 1.0).
+ * EPP_ERR_INVALID_ARGUMENT for v_max <= 0 or a_max <= 0. */
+epp_status epp_traj_scale_to_limits(double* seg_times, double* coeffs, const int32_t* wp_offsets,
+                                    int32_t n_tracks, double v_max, double a_max, double* scale,
+                                    int32_t* status, void* stream);
 
 /* ---- batch planner building blocks (device pointers) ------------------------------- */
 /* Replace OMPL's sampler / nearest-neighbour structure behind PathPlanner::planPath
@@ -312,6 +341,18 @@ epp_status epp_generate_trajectory_host(const double* wp, int32_t n_wp, double v
 epp_status epp_generate_trajectory_times_host(const double* wp, int32_t n_wp, const double* seg_times, double dt,
                                               double t0, const double v0[3], const double a0[3], double** rows,
                                               int64_t* n_rows);
+/* epp_generate_trajectory_host with v_max and a_max enforced on the fitted trajectory:
+ * fit, then Trajectory::scaleSegmentTimesToMeetConstraints (external/poly_traj/src/
+ * trajectory.cpp:385-429; epp_traj_scale_to_limits above), then evaluateRange sampling of
+ * the scaled trajectory (the row count follows the scaled times).  Three launches over
+ * pinned host buffers; the fit is the batch kernel's (epp_minsnap_batch), so the rows are
+ * those of epp_sample_batch on epp_traj_scale_to_limits' output.  *scale_out (may be
+ * NULL): the factor applied to the segment times (1.0: the fit was within the limits).
+ * Errors as epp_generate_trajectory_host; also EPP_ERR_INVALID_ARGUMENT for v_max <= 0 or
+ * a_max <= 0, EPP_ERR_RUNTIME when the limits are not met after 20 rounds. */
+epp_status epp_generate_trajectory_limited_host(const double* wp, int32_t n_wp, double v_max, double a_max,
+                                                double dt, double t0, const double v0[3], const double a0[3],
+                                                double** rows, int64_t* n_rows, double* scale_out);
 /* The C5 online step's two GPU calls in ONE launch (an addition of this build; the
  * reference makes them one after the other: PathPlanner::checkTrajectoryValidity,
  * src/PathPlanner.cpp:267-280, then poly_traj::generateTrajectory, src/
