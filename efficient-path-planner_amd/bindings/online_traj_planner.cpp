@@ -226,6 +226,34 @@ PYBIND11_MODULE(online_traj_planner, m) {
             },
             py::arg("s1"), py::arg("s2"))
         .def(
+            "check_points",  // World::checkPoints: one flag per point
+            [](const epp::PathPlanner& self, const py::object& points, bool canPassGate) {
+                Matrix p = to_matrix(points);
+                if (p.cols != 3) throw std::invalid_argument("points must be an (n, 3) array");
+                py::array_t<uint8_t> out((py::ssize_t)p.rows);
+                {
+                    py::gil_scoped_release release;
+                    self.worldPtr->checkPoints(p.data.data(), (int64_t)p.rows, canPassGate, out.mutable_data());
+                }
+                return out;
+            },
+            py::arg("points"), py::arg("canPassGate"))
+        .def(
+            "check_rays",  // World::checkRays (checkRayValid per ray): one flag per ray
+            [](const epp::PathPlanner& self, const py::object& s1, const py::object& s2, bool canPassGate) {
+                Matrix a = to_matrix(s1), b = to_matrix(s2);
+                if (a.cols != 3 || b.cols != 3 || a.rows != b.rows)
+                    throw std::invalid_argument("s1 and s2 must be (n, 3) arrays of one length");
+                py::array_t<uint8_t> out((py::ssize_t)a.rows);
+                {
+                    py::gil_scoped_release release;
+                    self.worldPtr->checkRays(a.data.data(), b.data.data(), (int64_t)a.rows, canPassGate,
+                                             out.mutable_data());
+                }
+                return out;
+            },
+            py::arg("s1"), py::arg("s2"), py::arg("canPassGate") = false)
+        .def(
             "plan_once",  // one batch-planner attempt with an explicit sample count and seed
             [](const epp::PathPlanner& self, const py::object& start, const py::object& goal, int64_t samples,
                uint64_t seed) -> py::object {

@@ -24,6 +24,7 @@
 
 #include "epp/PathPlanner.h"
 #include "epp/trajectory_generator.h"
+#include "completion.h"
 #include "epp_internal.h"
 #include "host_scratch.h"
 
@@ -157,30 +158,22 @@ public:
             check(epp_malloc(&dev_, dev_bytes), "planner batch workspace");
             dcap_ = dev_bytes;
         }
-        if (host_bytes > hcap_) {
-            host_bytes = std::max(host_bytes, hcap_ + hcap_ / 2);
-            if (host_) (void)hipHostFree(host_);
-            host_ = nullptr;
-            hcap_ = 0;
-            if (hipHostMalloc(&host_, host_bytes, hipHostMallocDefault) != hipSuccess) {
-                host_ = nullptr;
-                throw std::runtime_error("planner batch: hipHostMalloc failed");
-            }
-            std::memset(host_, 0, host_bytes);  // (completion slots: no stale sequence numbers)
-            hcap_ = host_bytes;
-        }
+        // (zeroed: the completion slots hold no stale sequence number)
+        if (host_bytes > host_.cap &&
+            host_.grow(std::max(host_bytes, host_.cap + host_.cap / 2), true) != hipSuccess)
+            throw std::runtime_error("planner batch: hipHostMalloc failed");
     }
     void* dev() const { return dev_; }
-    char* host() const { return static_cast<char*>(host_); }
-    uint32_t next_seq() { return ++seq_ ? seq_ : ++seq_; }  // (never 0: fresh slots read 0)
+    char* host() const { return host_.as<char>(); }
+    uint32_t next_seq() { return epp::next_seq(seq_); }
     // Buffers of the whole-table search of one problem per planner thread (w), sized here
     // for n nodes: allocated with the batch, not on the planner threads when a search falls
     // back (a first allocation of pinned memory there took milliseconds).
     struct Area {
         void* dev = nullptr;
-        void* pin = nullptr;
+        PinnedBuf pin;
         void* stream = nullptr;
-        size_t dcap = 0, pcap = 0;
+        size_t dcap = 0;
         bool cold = true;  // no whole-table search has run on it yet
     };
     static size_t r256(size_t b) { return (b + 255) & ~size_t(255); }
@@ -209,19 +202,12 @@ public:
                 check(epp_malloc(&a.dev, db), "planner fallback workspace");
                 a.dcap = db;
             }
-            if (pb > a.pcap) {
-                if (a.pin) (void)hipHostFree(a.pin);
-                a.pin = nullptr;
-                a.pcap = 0;
-                if (hipHostMalloc(&a.pin, pb, hipHostMallocDefault) != hipSuccess) {
-                    a.pin = nullptr;
-                    throw std::runtime_error("planner fallback: hipHostMalloc failed");
-                }
-                a.pcap = pb;
+            if (pb > a.pin.cap) {
+                if (a.pin.grow(pb) != hipSuccess) throw std::runtime_error("planner fallback: hipHostMalloc failed");
                 // one DMA over the whole buffer now: the first transfers into fresh pinned
                 // memory are slow (a first fallback took ~10 ms), and they belong here, with
                 // the allocation (the cold first plan), not in a search
-                check(epp_memcpy_d2h_async(a.pin, a.dev, std::min(pb, a.dcap), a.stream), "planner fallback warm-up");
+                check(epp_memcpy_d2h_async(a.pin.p, a.dev, std::min(pb, a.dcap), a.stream), "planner fallback warm-up");
                 check(epp_stream_sync(a.stream), "planner fallback warm-up");
                 // (cold stays as it was: a grown area -- a retry with doubled samples -- has
                 // had its warm-up search; a new one starts cold)
@@ -235,11 +221,9 @@ public:
     }
     ~BatchScratch() {
         if (dev_) epp_free(dev_);
-        if (host_) (void)hipHostFree(host_);
         if (stream_) epp_stream_destroy(stream_);
         for (Area& a : areas_) {
             if (a.dev) epp_free(a.dev);
-            if (a.pin) (void)hipHostFree(a.pin);
             if (a.stream) epp_stream_destroy(a.stream);
         }
     }
@@ -247,9 +231,9 @@ public:
 private:
     std::vector<Area> areas_;
     void* dev_ = nullptr;
-    void* host_ = nullptr;
+    PinnedBuf host_;
     void* stream_ = nullptr;
-    size_t dcap_ = 0, hcap_ = 0;
+    size_t dcap_ = 0;
     uint32_t seq_ = 0;
 };
 
@@ -750,27 +734,14 @@ void PathPlanner::planChunk(const std::vector<std::pair<Vec3, Vec3>>& problems, 
         // (a deadline: a batch that has not completed in kBatchDeadlineS raises instead of
         // polling forever; the scratch it writes into stays allocated)
         constexpr double kBatchDeadlineS = 30.0;
-        const uint32_t* done = reinterpret_cast<const uint32_t*>(H + L.h_done);
-        const auto tw0 = std::chrono::steady_clock::now();
-        for (uint64_t spin = 0;; ++spin) {
-            int b = 0;
-            while (b < L.done_n && __atomic_load_n(done + b, __ATOMIC_ACQUIRE) == seq) ++b;
-            if (b == L.done_n) break;
-            if ((spin & 1023) == 1023) {
-                const hipError_t q = hipStreamQuery(static_cast<hipStream_t>(st));
-                if (q == hipErrorNotReady) {
-                    if (std::chrono::duration<double>(std::chrono::steady_clock::now() - tw0).count() > kBatchDeadlineS)
-                        throw std::runtime_error("planner batch: not complete after 30 s (device hung?)");
-                    continue;
-                }
-                if (q != hipSuccess) throw std::runtime_error(std::string("planner batch: ") + hipGetErrorString(q));
-                b = 0;
-                while (b < L.done_n && __atomic_load_n(done + b, __ATOMIC_ACQUIRE) == seq) ++b;
-                if (b != L.done_n) throw std::runtime_error("planner batch: completed without its completion slots");
-                break;
-            }
-            _mm_pause();
-        }
+        const WaitResult r = wait_done(reinterpret_cast<const uint32_t*>(H + L.h_done), L.done_n, seq,
+                                       static_cast<hipStream_t>(st), kBatchDeadlineS);
+        if (r.kind == WaitResult::kDeadline)
+            throw std::runtime_error("planner batch: not complete after 30 s (device hung?)");
+        if (r.kind == WaitResult::kHipError)
+            throw std::runtime_error(std::string("planner batch: ") + hipGetErrorString(r.err));
+        if (r.kind == WaitResult::kNoSlots)
+            throw std::runtime_error("planner batch: completed without its completion slots");
         plan_batch_trace_print();
         for (int p = 0; p < S; ++p) first[p + 1] = first[p] + std::min<int64_t>(hv(0, p), segs[p].cap);
         // Cold areas (this thread's first plans): one whole-table search on problem 0's
@@ -865,7 +836,7 @@ bool PathPlanner::wholeTableSearch(const double* d_nodes, int32_t n, const doubl
     void* st = area.stream;
     const size_t m = (size_t)n * k;
     const size_t ws_bytes = (size_t)epp_knn_workspace_size(n);
-    if (BatchScratch::area_dev_bytes(n, k) > area.dcap || BatchScratch::area_pin_bytes(n, k) > area.pcap)
+    if (BatchScratch::area_dev_bytes(n, k) > area.dcap || BatchScratch::area_pin_bytes(n, k) > area.pin.cap)
         throw std::runtime_error("planPath: fallback workspace too small");
     char* dp = static_cast<char*>(area.dev);
     int64_t* d_ecnt = reinterpret_cast<int64_t*>(dp);
@@ -891,7 +862,7 @@ bool PathPlanner::wholeTableSearch(const double* d_nodes, int32_t n, const doubl
         check(ks, "motion check");
     }
     // the downloads queued back to back, one synchronisation
-    char* hp = static_cast<char*>(area.pin);
+    char* hp = area.pin.as<char>();
     int64_t* ecnt = reinterpret_cast<int64_t*>(hp);
     double overlap_ms = 0;  // (the rows' search, while the device worked: not device time)
     if (rows_sym) {  // the edge counts first, the caller's search on the rows meanwhile: no

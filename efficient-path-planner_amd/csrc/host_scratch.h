@@ -12,6 +12,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include "epp.h"
+#include "pinned_buf.h"
 
 namespace epp {
 
@@ -67,23 +68,14 @@ public:
     // reallocating pinned memory takes ~0.3 ms and synchronises the device (the second plan
     // of a generator paid it in its shortcut's checks).
     void* pinned(int slot, size_t bytes) {
-        if (bytes > pcap_[slot]) {
-            bytes = std::max(bytes, std::max<size_t>(pcap_[slot] + pcap_[slot] / 2, size_t(1) << 20));
-            if (pin_[slot]) (void)hipHostFree(pin_[slot]);
-            pin_[slot] = nullptr;
-            pcap_[slot] = 0;
-            if (hipHostMalloc(&pin_[slot], bytes, hipHostMallocDefault) != hipSuccess) {
-                pin_[slot] = nullptr;
-                throw std::runtime_error("pinned host staging: hipHostMalloc failed");
-            }
-            pcap_[slot] = bytes;
-        }
-        return pin_[slot];
+        PinnedBuf& b = pin_[slot];
+        if (bytes > b.cap &&
+            b.grow(std::max(bytes, std::max<size_t>(b.cap + b.cap / 2, size_t(1) << 20))) != hipSuccess)
+            throw std::runtime_error("pinned host staging: hipHostMalloc failed");
+        return b.p;
     }
     ~ThreadScratch() {
         if (buf_) epp_free(buf_);
-        for (void* p : pin_)
-            if (p) (void)hipHostFree(p);
         if (stream_) epp_stream_destroy(stream_);
         if (cstream_) epp_stream_destroy(cstream_);
     }
@@ -93,8 +85,7 @@ private:
     void* cstream_ = nullptr;
     void* buf_ = nullptr;
     size_t cap_ = 0, used_ = 0;
-    void* pin_[3] = {nullptr, nullptr, nullptr};
-    size_t pcap_[3] = {0, 0, 0};
+    PinnedBuf pin_[3];
 };
 
 }  // namespace epp

@@ -20,7 +20,6 @@
 // one lane runs the sequential `acc += dt` / segment roll-over recurrence (so sample
 // times and counts are bit-identical), and the wavefront evaluates the rows.
 #include <hip/hip_runtime.h>
-#include <immintrin.h>
 
 #include <algorithm>
 #include <cmath>
@@ -32,6 +31,7 @@
 #include "cached_ws.h"
 #include "epp_internal.h"
 #include "minsnap_consts.h"
+#include "pinned_buf.h"
 #include "small_body.h"
 
 namespace epp {
@@ -875,13 +875,11 @@ __device__ __forceinline__ void refit_body(const RefitArgs& a, int g, double* sm
         }
     }
     EPP_TL(13);
-    // completion: this slice's rows (and workgroup 0's status) are visible system-wide
-    // before the slot is
-    wg_stores_settled();
-    if (tid == 0) {
-        if (g == 0) __hip_atomic_store(a.info, (int64_t)st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(a.done + g, a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    // completion: this slice's rows and workgroup 0's status (stored by the lane that
+    // publishes: slot 0 holding seq implies the status) are visible system-wide before the
+    // slot is
+    if (tid == 0 && g == 0) a.info[0] = st;
+    publish_done(a.done + g, a.seq);
 }
 
 template <bool LDS>
@@ -917,8 +915,7 @@ __global__ __launch_bounds__(kRefitBlock) void k_check_refit(RefitArgs a, CheckA
     }
     states_small_body<true, false>(smem, (int)blockIdx.x - a.writers, c.recs, c.n_obb, c.rg, c.ro, c.xyz, c.n, c.per, 0,
                                    c.md, c.valid, nullptr, nullptr);
-    wg_stores_settled();
-    if (threadIdx.x == 0) __hip_atomic_store(a.done + blockIdx.x, a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    publish_done(a.done + blockIdx.x, a.seq);
 }
 
 bool g_consts_ready[64];
@@ -1043,116 +1040,69 @@ epp_status minsnap_batch(const double* wp, const int32_t* wp_offsets, int32_t n_
     return st;
 }
 
-// Per-host-thread state of the single-track latency path: a stream, pinned host buffers
-// the kernel reads / writes directly and the device segment scratch of long tracks.
-struct RefitCache {
+// Per-host-thread state of the single-track host paths: a stream bound to the thread's
+// current device, two pinned host buffers the kernels read / write directly (sized exactly)
+// and a device scratch; all released and recreated when the thread's device changes.
+struct StreamBufs {
     hipStream_t s = nullptr;
     int dev = -1;
-    double* h_in = nullptr;
-    size_t in_cap = 0;
-    char* h_out = nullptr;  // [status (8 B) | pad | writer slots (64 B) | rows (at +128)]
-    size_t out_cap = 0;
-    double* d_scr = nullptr;  // segment scratch (one per workgroup) of long tracks
+    PinnedBuf h_in, h_out;
+    double* d_scr = nullptr;
     size_t scr_cap = 0;
-    uint32_t seq = 0;
-    std::vector<double> T, tin, tac;  // host side of the refit: times and samples
-    std::vector<int32_t> seg;
     void release() {
         if (s) (void)hipStreamSynchronize(s);
-        if (h_in) (void)hipHostFree(h_in);
-        if (h_out) (void)hipHostFree(h_out);
+        h_in.free();
+        h_out.free();
         if (d_scr) (void)hipFree(d_scr);
         if (s) (void)hipStreamDestroy(s);
-        h_in = nullptr;
-        h_out = nullptr;
         d_scr = nullptr;
         s = nullptr;
-        in_cap = out_cap = scr_cap = 0;
-        seq = 0;
+        scr_cap = 0;
     }
-    ~RefitCache() { release(); }
-    epp_status ensure(size_t in_b, size_t out_b, size_t scr_b) {
+    ~StreamBufs() { release(); }
+    hipError_t bind() {
         int d = 0;
         (void)hipGetDevice(&d);
         if (d != dev) release();  // bound to another device: start over
         dev = d;
-        hipError_t e = hipSuccess;
-        if (!s) e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-        auto grow_host = [&](auto*& p, size_t& cap, size_t need) {
-            if (e != hipSuccess || need <= cap) return;
-            if (s) (void)hipStreamSynchronize(s);  // (the previous call's kernel has ended)
-            if (p) (void)hipHostFree(p);
-            p = nullptr;
-            cap = 0;
-            e = hipHostMalloc(reinterpret_cast<void**>(&p), need, hipHostMallocDefault);
-            if (e == hipSuccess) cap = need;
-        };
-        grow_host(h_in, in_cap, in_b);
-        grow_host(h_out, out_cap, out_b);
+        if (s) return hipSuccess;
+        const hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+        if (e != hipSuccess) s = nullptr;
+        return e;
+    }
+    // (after bind) at least these sizes; a new h_out block starts zeroed when zero_out
+    hipError_t ensure(size_t in_b, size_t out_b, size_t scr_b, bool zero_out = false) {
+        if (in_b > h_in.cap || out_b > h_out.cap || scr_b > scr_cap)
+            (void)hipStreamSynchronize(s);  // (the previous call's kernel has ended)
+        hipError_t e = h_in.grow(in_b);
+        if (e == hipSuccess) e = h_out.grow(out_b, zero_out);
         if (e == hipSuccess && scr_b > scr_cap) {
-            (void)hipStreamSynchronize(s);
             if (d_scr) (void)hipFree(d_scr);
             d_scr = nullptr;
             scr_cap = 0;
             e = hipMalloc(reinterpret_cast<void**>(&d_scr), scr_b);
             if (e == hipSuccess) scr_cap = scr_b;
         }
-        if (e != hipSuccess) {
-            set_error(std::string("generateTrajectory: buffers: ") + hipGetErrorString(e));
-            return EPP_ERR_HIP;
-        }
-        return EPP_OK;
+        return e;
     }
+};
+epp_status buffers_error(hipError_t e) {
+    set_error(std::string("generateTrajectory: buffers: ") + hipGetErrorString(e));
+    return EPP_ERR_HIP;
+}
+
+// The single-track latency path (check_and_generate_into): h_in the kernel's inputs, h_out
+// [status (8 B) | pad | completion slots (at +64) | check flags (at +256) | rows], d_scr the
+// segment scratch (one per workgroup) of long tracks.
+struct RefitCache : StreamBufs {
+    uint32_t seq = 0;
+    std::vector<double> T, tin, tac;  // host side of the refit: times and samples
+    std::vector<int32_t> seg;
 };
 
-// Per-host-thread state of epp_generate_trajectory_limited_host: a stream and two pinned
-// host buffers (the track's inputs, times, coefficients and flags; the rows) that the three
-// kernels read and write directly.
-struct LimitedCache {
-    hipStream_t s = nullptr;
-    int dev = -1;
-    char* h_io = nullptr;
-    size_t io_cap = 0;
-    char* h_rows = nullptr;
-    size_t rows_cap = 0;
-    void release() {
-        if (s) (void)hipStreamSynchronize(s);
-        if (h_io) (void)hipHostFree(h_io);
-        if (h_rows) (void)hipHostFree(h_rows);
-        if (s) (void)hipStreamDestroy(s);
-        h_io = h_rows = nullptr;
-        s = nullptr;
-        io_cap = rows_cap = 0;
-    }
-    ~LimitedCache() { release(); }
-    epp_status stream_on_device() {
-        int d = 0;
-        (void)hipGetDevice(&d);
-        if (d != dev) release();
-        dev = d;
-        if (!s && hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) {
-            s = nullptr;
-            set_error("generateTrajectory: stream");
-            return EPP_ERR_HIP;
-        }
-        return EPP_OK;
-    }
-    epp_status grow(char*& p, size_t& cap, size_t need) {
-        if (need <= cap) return EPP_OK;
-        (void)hipStreamSynchronize(s);
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-        const hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&p), need, hipHostMallocDefault);
-        if (e != hipSuccess) {
-            p = nullptr;
-            set_error(std::string("generateTrajectory: buffers: ") + hipGetErrorString(e));
-            return EPP_ERR_HIP;
-        }
-        cap = need;
-        return EPP_OK;
-    }
-};
+// epp_generate_trajectory_limited_host: h_in the track's inputs, times, coefficients and
+// flags, h_out the rows; the three kernels read and write them directly.
+using LimitedCache = StreamBufs;
 
 }  // namespace
 }  // namespace epp
@@ -1297,10 +1247,13 @@ epp_status epp::check_and_generate_into(const FusedCheck* chk, const double* wp,
     const size_t in_refit = (refit_in_doubles(n_wp, R) + 1) & ~size_t(1);  // (16-byte aligned points after it)
     constexpr size_t kRowsAt = 256;  // h_out: [status | pad | slots (<= 48 x 4 B) | flags | rows]
     const size_t rows_at = kRowsAt + (((size_t)nck + 255) & ~size_t(255));
-    if ((rc = c.ensure((in_refit + 3 * (size_t)nck) * 8, (size_t)R * 80 + rows_at,
-                       lds ? 0 : (size_t)G * refit_scr_doubles(M, big) * 8)))
-        return rc;
-    double* in = c.h_in;
+    hipError_t e = c.bind();
+    if (e == hipSuccess)  // (a new h_out zeroed: its completion slots)
+        e = c.ensure((in_refit + 3 * (size_t)nck) * 8, (size_t)R * 80 + rows_at,
+                     lds ? 0 : (size_t)G * refit_scr_doubles(M, big) * 8, true);
+    if (e != hipSuccess) return buffers_error(e);
+    double* in = c.h_in.as<double>();
+    char* const h_out = c.h_out.as<char>();
     std::memcpy(in, wp, (size_t)n_wp * 24);
     for (int k = 0; k < 3; ++k) {
         in[3 * n_wp + k] = v0 ? v0[k] : 0.0;
@@ -1318,13 +1271,12 @@ epp_status epp::check_and_generate_into(const FusedCheck* chk, const double* wp,
     a.W = n_wp;
     a.R = R;
     a.writers = G;
-    if (++c.seq == 0) c.seq = 1;
-    a.seq = c.seq;
+    a.seq = next_seq(c.seq);
     a.t0 = t0;
     if (n_wp <= kRefitArgW) std::memcpy(a.small, in, (size_t)(3 * n_wp + 6 + M) * 8);
-    a.info = reinterpret_cast<int64_t*>(c.h_out);
-    a.done = reinterpret_cast<uint32_t*>(c.h_out + 64);
-    a.out = reinterpret_cast<double*>(c.h_out + rows_at);
+    a.info = reinterpret_cast<int64_t*>(h_out);
+    a.done = reinterpret_cast<uint32_t*>(h_out + 64);
+    a.out = reinterpret_cast<double*>(h_out + rows_at);
     a.scratch = c.d_scr;
     a.big = big ? 1 : 0;
     {  // the latency path solves without the refinement step: it cost 6-7 us of a ~30 us
@@ -1350,7 +1302,7 @@ epp_status epp::check_and_generate_into(const FusedCheck* chk, const double* wp,
         ck.md = chk->min_distance;
         ck.xyz = pts;
         ck.n = nck;
-        ck.valid = reinterpret_cast<uint8_t*>(c.h_out + kRowsAt);
+        ck.valid = reinterpret_cast<uint8_t*>(h_out + kRowsAt);
         shm = std::max(shm, small_shm(sw.n_obb));
         if (lds) {
             allow_lds(k_check_refit<true>);
@@ -1366,32 +1318,21 @@ epp_status epp::check_and_generate_into(const FusedCheck* chk, const double* wp,
         allow_lds(k_refit<false>);
         hipLaunchKernelGGL(k_refit<false>, dim3(G), dim3(kRefitBlock), shm, c.s, a);
     }
-    hipError_t e = hipGetLastError();
-    // wait for the status word and every workgroup's slot (polled; the stream is queried
-    // every ~1k polls so a failed launch ends the wait)
-    const int slots = G + Gc;
-    auto complete = [&]() {
-        if (__atomic_load_n(a.info, __ATOMIC_ACQUIRE) == -100) return false;
-        for (int g = 0; g < slots; ++g)
-            if (__atomic_load_n(a.done + g, __ATOMIC_ACQUIRE) != a.seq) return false;
-        return true;
-    };
-    for (uint64_t spin = 0; e == hipSuccess && !complete(); ++spin) {
-        if ((spin & 1023) == 1023) {
-            const hipError_t q = hipStreamQuery(c.s);
-            if (q == hipErrorNotReady) continue;
-            if (q != hipSuccess) e = q;
-            else if (!complete()) e = hipErrorUnknown;  // finished without its completion words
-            break;
-        }
-        _mm_pause();
+    e = hipGetLastError();
+    // wait for every workgroup's slot; slot 0's release follows the status store of the
+    // same lane, so the status is visible with it (still -100: it was never written)
+    int64_t info = -100;
+    if (e == hipSuccess) {
+        const WaitResult r = wait_done(a.done, G + Gc, a.seq, c.s, 0.0);
+        if (r.kind == WaitResult::kHipError) e = r.err;
+        else if (r.kind != WaitResult::kDone || (info = a.info[0]) == -100)
+            e = hipErrorUnknown;  // finished without its completion words
     }
-    const int64_t info = __atomic_load_n(a.info, __ATOMIC_ACQUIRE);
     if (e != hipSuccess) {
         set_error(std::string("generateTrajectory: ") + hipGetErrorString(e));
         return EPP_ERR_HIP;
     }
-    if (Gc > 0) std::memcpy(chk->valid, c.h_out + kRowsAt, (size_t)nck);
+    if (Gc > 0) std::memcpy(chk->valid, h_out + kRowsAt, (size_t)nck);
     if (info != 0) {
         set_error(info == -2 ? "Segment times need to be greater than zero" : "min-snap solve failed");
         return EPP_ERR_RUNTIME;
@@ -1499,11 +1440,15 @@ epp_status epp_generate_trajectory_limited_host(const double* wp, int32_t n_wp, 
             return EPP_ERR_RUNTIME;
         }
     static thread_local LimitedCache c;
-    epp_status rc = c.stream_on_device();
-    if (rc) return rc;
+    if (c.bind() != hipSuccess) {
+        set_error("generateTrajectory: stream");
+        return EPP_ERR_HIP;
+    }
+    epp_status rc;
     const size_t nd = (size_t)3 * n_wp + 6 + (size_t)M * 31 + 2;  // doubles before the int32 words
-    if ((rc = c.grow(c.h_io, c.io_cap, nd * 8 + 16))) return rc;
-    double* h_wp = reinterpret_cast<double*>(c.h_io);
+    hipError_t e = c.ensure(nd * 8 + 16, 0, 0);
+    if (e != hipSuccess) return buffers_error(e);
+    double* h_wp = c.h_in.as<double>();
     double* h_v0 = h_wp + 3 * n_wp;
     double* h_a0 = h_v0 + 3;
     double* h_T = h_a0 + 3;
@@ -1526,7 +1471,7 @@ epp_status epp_generate_trajectory_limited_host(const double* wp, int32_t n_wp, 
                             "generateTrajectory", M)))
         return rc;
     if ((rc = epp_traj_scale_to_limits(h_T, h_C, h_off, 1, v_max, a_max, h_scale, h_st + 1, c.s))) return rc;
-    hipError_t e = hipStreamSynchronize(c.s);
+    e = hipStreamSynchronize(c.s);
     if (e != hipSuccess) {
         set_error(std::string("generateTrajectory: ") + hipGetErrorString(e));
         return EPP_ERR_HIP;
@@ -1555,13 +1500,15 @@ epp_status epp_generate_trajectory_limited_host(const double* wp, int32_t n_wp, 
         return EPP_ERR_RUNTIME;
     }
     if (R) {
-        if ((rc = ensure_consts()) || (rc = c.grow(c.h_rows, c.rows_cap, (size_t)R * 80))) {
+        rc = ensure_consts();
+        if (!rc && (e = c.ensure(0, (size_t)R * 80, 0)) != hipSuccess) rc = buffers_error(e);
+        if (rc) {
             std::free(rows);
             return rc;
         }
         const size_t shm = ((size_t)kNC + ((M + 1) & ~1) + 3 * kRowChunk + 2) * 8;
         hipLaunchKernelGGL(k_sample_rows, dim3(1), dim3(kWave), shm, c.s, h_T, h_C, h_off, 1, dt, h_t0,
-                           (const int64_t*)nullptr, reinterpret_cast<double*>(c.h_rows), R);
+                           (const int64_t*)nullptr, c.h_out.as<double>(), R);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(c.s);
         if (e != hipSuccess) {
@@ -1569,7 +1516,7 @@ epp_status epp_generate_trajectory_limited_host(const double* wp, int32_t n_wp, 
             set_error(std::string("generateTrajectory: ") + hipGetErrorString(e));
             return EPP_ERR_HIP;
         }
-        std::memcpy(rows, c.h_rows, (size_t)R * 80);
+        std::memcpy(rows, c.h_out.p, (size_t)R * 80);
     }
     if (scale_out) *scale_out = *h_scale;
     *rows_out = rows;

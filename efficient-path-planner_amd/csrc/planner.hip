@@ -2566,9 +2566,8 @@ __global__ __launch_bounds__(kCompactThreads) void k_pb_number(PlanBatchDev P, u
 // rows' problem and compact node index (u32), the masked rows in compact indices (u16,
 // renumbered here through `map` as they are copied), every problem's referenced nodes
 // (24 B each, at its own offset).  16-byte stores (the device parts are 16-byte padded).
-// Each workgroup then publishes `seq` in its completion slot (host memory, system scope,
-// after a system fence over its stores): the host polls the slots instead of synchronising
-// the stream.
+// Each workgroup then publishes `seq` in its completion slot (publish_done, completion.h):
+// the host polls the slots instead of synchronising the stream.
 __global__ __launch_bounds__(256) void k_pb_emit(PlanBatchDev P, unsigned long long* __restrict__ hdr,
                                                   uint4* __restrict__ h_slot, uint4* __restrict__ h_rows,
                                                   uint4* __restrict__ h_need, uint32_t* __restrict__ done,
@@ -2630,8 +2629,7 @@ __global__ __launch_bounds__(256) void k_pb_emit(PlanBatchDev P, unsigned long l
             h_need[at] = d_need[at];
         }
     }
-    wg_stores_settled();
-    if (threadIdx.x == 0) __hip_atomic_store(done + blockIdx.x, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    publish_done(done + blockIdx.x, seq);
 }
 
 constexpr int kPbEmitMax = 1024;  // emit workgroups (one completion slot each)

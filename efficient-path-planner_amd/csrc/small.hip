@@ -12,14 +12,16 @@
 // Each workgroup stages the records in LDS; every lane then walks all OBBs in step (the
 // same record for the whole wave: LDS broadcast), and the exact test runs only when some
 // lane's query passes the AABB test (a wave-uniform branch).
-#include <immintrin.h>
-
 #include "collision_common.h"
+#include "pinned_buf.h"
 #include "small_body.h"
 #include "small_sync.h"
 
 namespace epp {
 namespace {
+
+// the workgroup's completion slot (done == NULL: an asynchronous launch, nobody polls)
+__device__ __forceinline__ uint32_t* own_slot(uint32_t* done) { return done ? done + blockIdx.x : nullptr; }
 
 template <bool MINDIST, bool COMPACT>
 __global__ __launch_bounds__(kSmallBlock) void k_states_small(const double* __restrict__ recs, int n_obb, double rg,
@@ -32,7 +34,7 @@ __global__ __launch_bounds__(kSmallBlock) void k_states_small(const double* __re
     extern __shared__ double srec[];
     states_small_body<MINDIST, COMPACT>(srec, blockIdx.x, recs, n_obb, rg, ro, xyz, n, per, can_pass, md, valid,
                                         compact_idx, n_valid);
-    publish_done(done, seq);
+    publish_done(own_slot(done), seq);
 }
 
 template <int MODE>
@@ -88,7 +90,7 @@ __global__ __launch_bounds__(kSmallBlock) void k_motions_small(const double* __r
         if (bits) atomicOr(&s_hit[j], bits);  // (LDS)
         __syncthreads();
         if (slice == 0 && act) valid[i] = (uint8_t)(s_hit[j] ^ 3u);
-        publish_done(done, seq);
+        publish_done(own_slot(done), seq);
         return;
     }
     const bool cp = can_pass != 0;
@@ -118,7 +120,7 @@ __global__ __launch_bounds__(kSmallBlock) void k_motions_small(const double* __r
     if (hit) s_hit[j] = 1u;
     __syncthreads();
     if (slice == 0 && act) valid[i] = s_hit[j] ? 0 : 1;
-    publish_done(done, seq);
+    publish_done(own_slot(done), seq);
 }
 
 // test hook (not for production use): EPP_STATES_KERNEL / EPP_MOTIONS_KERNEL set to
@@ -168,55 +170,30 @@ epp_status launch_motions_small(const SmallWorld& sw, int32_t mode, const double
 
 // ---- synchronous host path ----------------------------------------------------------
 namespace {
-// per host thread: pinned completion slots (one per workgroup) and the call counter
-struct DoneSlots {
-    uint32_t* p = nullptr;
-    uint32_t seq = 0;
-    ~DoneSlots() {
-        if (p) (void)hipHostFree(p);
-    }
-};
 constexpr int kMaxSmallGroups = (int)std::max<int64_t>(kSmallStates / kSmallBlock, kSmallMotions / 16);
 static_assert(kSmallStates / kSmallBlock <= kMaxSmallGroups && kSmallMotions / 16 <= kMaxSmallGroups,
               "completion slots for the small workgroups");
 
-// Polls the slots until every workgroup has published `seq`; a stream that completes or
-// fails without them ends the wait through hipStreamQuery (checked every ~1k polls).
-epp_status wait_done(const uint32_t* done, int groups, uint32_t seq, hipStream_t st, const char* what) {
-    for (uint64_t spin = 0;; ++spin) {
-        int b = 0;
-        while (b < groups && __atomic_load_n(done + b, __ATOMIC_ACQUIRE) == seq) ++b;
-        if (b == groups) return EPP_OK;
-        if ((spin & 1023) == 1023) {
-            const hipError_t q = hipStreamQuery(st);
-            if (q == hipErrorNotReady) continue;
-            if (q != hipSuccess) {
-                set_error(std::string(what) + ": " + hipGetErrorString(q));
-                return EPP_ERR_HIP;
-            }
-            b = 0;
-            while (b < groups && __atomic_load_n(done + b, __ATOMIC_ACQUIRE) == seq) ++b;
-            if (b == groups) return EPP_OK;
-            set_error(std::string(what) + ": kernel completed without its completion flags");
-            return EPP_ERR_RUNTIME;
-        }
-        _mm_pause();
-    }
-}
-
 template <typename Launch>
 epp_status run_sync(int64_t n, int per, hipStream_t st, const char* what, Launch&& launch) {
-    thread_local DoneSlots ds;
-    if (!ds.p && hipHostMalloc(reinterpret_cast<void**>(&ds.p), kMaxSmallGroups * sizeof(uint32_t),
-                               hipHostMallocDefault) != hipSuccess) {
-        ds.p = nullptr;
+    // per host thread: pinned completion slots (one per workgroup) and the call counter
+    thread_local PinnedBuf slots;
+    thread_local uint32_t counter = 0;
+    if (slots.grow(kMaxSmallGroups * sizeof(uint32_t), true) != hipSuccess) {
         set_error(std::string(what) + ": pinned completion slots: hipHostMalloc failed");
         return EPP_ERR_HIP;
     }
-    const uint32_t seq = ++ds.seq;
+    const uint32_t seq = next_seq(counter);
     const int groups = (int)((n + per - 1) / per);
-    if (const epp_status rc = launch(ds.p, seq)) return rc;
-    return wait_done(ds.p, groups, seq, st, what);
+    if (const epp_status rc = launch(slots.as<uint32_t>(), seq)) return rc;
+    const WaitResult r = wait_done(slots.as<uint32_t>(), groups, seq, st, 0.0);
+    if (r.kind == WaitResult::kDone) return EPP_OK;
+    if (r.kind == WaitResult::kHipError) {
+        set_error(std::string(what) + ": " + hipGetErrorString(r.err));
+        return EPP_ERR_HIP;
+    }
+    set_error(std::string(what) + ": kernel completed without its completion flags");
+    return EPP_ERR_RUNTIME;
 }
 }  // namespace
 

@@ -9,16 +9,6 @@ namespace {
 
 constexpr int kSmallBlock = 256;
 
-// Completion flag of a workgroup for the synchronous host path (done != NULL): every
-// thread's stores (the flags, in host memory) are made visible system-wide, then one
-// lane publishes `seq` in the workgroup's slot; the host polls the slots instead of
-// synchronising the stream.
-__device__ __forceinline__ void publish_done(uint32_t* done, uint32_t seq) {
-    if (!done) return;
-    wg_stores_settled();
-    if (threadIdx.x == 0) __hip_atomic_store(done + blockIdx.x, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
 // The records (n_obb x kRecDoubles doubles, 16-byte aligned start) into LDS: every 16-byte load
 // of up to 128 OBBs in flight at once (the records may be in host memory: one PCIe round
 // trip instead of one per few loads); `before` runs between the loads and the stores

@@ -721,3 +721,29 @@ def test_world_buffers_reused_across_worlds(geom, worlds):
         assert np.array_equal(w.check_states(pts), O.check_states(ref, rg, ro, pts, threads=8)), name
         assert np.array_equal(w.check_states(small), O.check_states(ref, rg, ro, small)), name
         w.close()
+
+
+def test_small_sync_queries_back_to_back_distinct_inputs(geom, worlds):
+    """256 consecutive checkPoints and checkRays calls of the C++ World on one host thread (the
+    polled small path: the same pinned staging and completion slots every call) with different
+    inputs each time; batch sizes cycle through one workgroup, a partial one and many
+    workgroups / slots.  Every call's flags are the oracle's for that call's inputs, bit for
+    bit: a read of the previous call's leftovers would show."""
+    import online_traj_planner as otp
+    from conftest import CONFIG
+    rg, ro, ws = worlds
+    gates, obstacles, (lo, hi) = ws["c2"]
+    pp = otp.PathPlanner(gates, obstacles, CONFIG)
+    ref = O.world_build(geom, np.array(gates, float), obstacles, rg, ro)
+    seen = set()
+    for call in range(256):
+        n = (1, 17, 256, 1024)[call % 4]
+        cp = bool((call // 4) % 2)
+        pts = synth.sample_states(1000 + call, lo, hi, n)
+        s1, s2 = synth.edges(2000 + call, 3000 + call, lo, hi, n, max_len=1.5)
+        exp_p = O.check_states(ref, rg, ro, pts, cp)
+        exp_r = O.check_motions(ref, rg, ro, s1, s2, cp)
+        assert np.array_equal(np.asarray(pp.check_points(pts, cp)), exp_p), (call, n)
+        assert np.array_equal(np.asarray(pp.check_rays(s1, s2, cp)), exp_r), (call, n)
+        seen |= {("p", int(v)) for v in np.unique(exp_p)} | {("r", int(v)) for v in np.unique(exp_r)}
+    assert seen == {("p", 0), ("p", 1), ("r", 0), ("r", 1)}

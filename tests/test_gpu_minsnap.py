@@ -464,3 +464,40 @@ def test_check_and_generate_large_check_unsupported_and_planner_fallback(cfg, ge
     traj = O.generate_trajectory(wp, 1.0, 2.0, 0.1)[:100]  # the trajectory's own lookahead
     ok, _ = pp.check_trajectory_validity_and_generate(traj, md, wp, 1.0, 2.0, 0.1)
     assert ok == pp.check_trajectory_validity(traj, md)
+
+
+def test_check_and_generate_back_to_back_distinct_tracks(cfg, geom):
+    """512 consecutive fused calls on one host thread reuse the same pinned buffers and
+    completion slots with different inputs: 64 tracks, cycled, alternating between 3 waypoints
+    (105 rows: one writer workgroup) and 5 waypoints (312 rows: three writers), track k being
+    the base track shifted by 0.05 k m in x, with 300 check points that move with it.  Every
+    call returns its own track's rows (the oracle's, computed once per track, within 1e-6, time
+    column exact; another track's differ by >= 0.05 in x) and its own points' flags (the
+    oracle's, bit for bit): a read of the previous call's leftovers would show."""
+    gates, obstacles, rg, ro = _c5_world(cfg, geom)
+    md = float(cfg["path_planner_properties"]["min_dist_check_traj_collision"])
+    ref = O.world_build(geom, gates, obstacles, rg, ro)
+    base = synth.random_track_waypoints(31, 4)
+    # 100 points on the base track and 200 that start left of an obstacle and sweep across it
+    # with the shifts, so that every track has its own flags
+    near = obstacles[np.arange(200) % len(obstacles), :3] * [1, 1, 0] + synth.sample_states(
+        32, [-3.3, -0.2, 0], [0.2, 0.2, 1.0], 200)
+    base_pts = np.vstack([O.generate_trajectory(base, 1.0, 2.0, 0.25)[:100, [0, 3, 6]], near])
+    assert base_pts.shape == (300, 3)
+    tracks = []
+    for k in range(64):
+        shift = np.array([0.05 * k, 0.0, 0.0])
+        wp, dt = (base[:3] + shift, 0.2) if k % 2 == 0 else (base + shift, 0.1)
+        rows = O.generate_trajectory(wp, 1.0, 2.0, dt)
+        assert (0 < len(rows) < 128) if k % 2 == 0 else (260 <= len(rows) <= 380)
+        pts = base_pts + shift
+        tracks.append((wp, dt, pts, rows, O.check_states_mindist(ref, pts, md)))
+    assert len({t[4].tobytes() for t in tracks}) == 64  # (stale flags would not pass as another track's)
+    w = capi.World(capi.build_obbs(geom, gates, obstacles), rg, ro)
+    for call in range(512):
+        wp, dt, pts, exp_rows, exp_flags = tracks[call % 64]
+        flags, rows = capi.check_and_generate_trajectory(w, pts, md, wp, 1.0, 2.0, dt)
+        assert np.array_equal(flags, exp_flags), call
+        assert rows.shape == exp_rows.shape and np.array_equal(rows[:, 9], exp_rows[:, 9]), call
+        assert np.abs(rows[:, :9] - exp_rows[:, :9]).max() < 1e-6, call
+    w.close()
