@@ -163,16 +163,19 @@ void World::checkRays(const double* s1, const double* s2, int64_t n, bool canPas
 }
 
 void World::checkRaysBoth(const double* s1, const double* s2, int64_t n, uint8_t* out) const {
+    if (n <= 0) return;
     const double* in[2] = {s1, s2};
-    bool two = false;  // (past the small path: two launches, below)
-    query(n, 2, [&](const double* const*, uint8_t*, void*) { two = true; },
-          [&](const double* const* d, uint8_t* flags, void* st) {
-              bool handled = false;
-              check(motions_small_sync(device(), 0, d[0], d[1], n, kCanPassBoth, flags, (hipStream_t)st, &handled),
-                    "checkRays");
-              return handled;
-          },
-          in, out);
+    // past the small path: two launches (below), without a round trip through query first
+    bool two = !motions_small_eligible(device(), n);
+    if (!two)  // (two: an update made the world too large since)
+        query(n, 2, [&](const double* const*, uint8_t*, void*) { two = true; },
+              [&](const double* const* d, uint8_t* flags, void* st) {
+                  bool handled = false;
+                  check(motions_small_sync(device(), 0, d[0], d[1], n, kCanPassBoth, flags, (hipStream_t)st, &handled),
+                        "checkRays");
+                  return handled;
+              },
+              in, out);
     if (!two) return;
     std::vector<uint8_t> t((size_t)n);
     checkRays(s1, s2, n, false, out);

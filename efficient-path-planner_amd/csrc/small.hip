@@ -207,6 +207,10 @@ epp_status states_small_sync(const epp_world* world, bool mindist, const double*
     });
 }
 
+bool motions_small_eligible(const epp_world* world, int64_t n) {
+    return n > 0 && n <= kSmallMotions && small_motions(small_world(world), n);
+}
+
 epp_status motions_small_sync(const epp_world* world, int32_t mode, const double* s1, const double* s2, int64_t n,
                               int32_t can_pass, uint8_t* valid, hipStream_t st, bool* handled) {
     const SmallWorld sw = small_world(world);

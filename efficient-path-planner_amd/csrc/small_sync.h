@@ -18,4 +18,7 @@ epp_status states_small_sync(const epp_world* world, bool mindist, const double*
                              double md, uint8_t* valid, hipStream_t st, bool* handled);
 epp_status motions_small_sync(const epp_world* world, int32_t mode, const double* s1, const double* s2, int64_t n,
                               int32_t can_pass, uint8_t* valid, hipStream_t st, bool* handled);
+// whether motions_small_sync would handle n edges on the world as it is now (a later update
+// may still change that: *handled has the last word)
+bool motions_small_eligible(const epp_world* world, int64_t n);
 }  // namespace epp

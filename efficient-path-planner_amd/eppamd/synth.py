@@ -61,7 +61,7 @@ def track_world(seed: int, n_gates: int = 8, n_obstacles: int = 24, a: float = 4
     k = 0
     while k < n_obstacles:
         p = rs.uniform(-6, 6, size=2)
-        if np.min(np.hypot(gates[:, 0] - p[0], gates[:, 1] - p[1])) < clearance + 0.45:
+        if n_gates and np.min(np.hypot(gates[:, 0] - p[0], gates[:, 1] - p[1])) < clearance + 0.45:
             continue
         obstacles[k, :2] = p
         k += 1

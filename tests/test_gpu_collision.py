@@ -12,6 +12,7 @@ import oracle as O
 from eppamd import capi, config, synth
 
 from conftest import GOLDEN
+from small_path_inputs import adversarial_points as _adversarial_points, gate_openings as _gate_openings
 
 pytestmark = pytest.mark.gpu
 
@@ -25,27 +26,6 @@ def _worlds(cfg, geom):
     g3, o3 = synth.track_world(42, n_obstacles=472)
     out["c3"] = (g3, o3, synth.C2_BOUNDS)
     return rg, ro, out
-
-
-def _adversarial_points(ref_w):
-    """Points exactly on / one ulp around every AABB face and corner."""
-    pts = []
-    for o in ref_w:
-        mid = (o["aabb_lo"] + o["aabb_hi"]) / 2
-        for k in range(3):
-            for v in (o["aabb_lo"][k], o["aabb_hi"][k]):
-                for w in (v, np.nextafter(v, np.inf), np.nextafter(v, -np.inf)):
-                    p = mid.copy()
-                    p[k] = w
-                    pts.append(p)
-        pts += [o["aabb_lo"].copy(), o["aabb_hi"].copy(), np.nextafter(o["aabb_hi"], -np.inf),
-                np.nextafter(o["aabb_lo"], np.inf), o["center"].copy()]
-        # points on the inflated OBB faces in local coordinates
-        c, s = o["rot"][0], o["rot"][3]
-        for sx in (-1, 1):
-            l = np.array([sx * (o["half"][0] + 0.2), 0.3 * o["half"][1], 0.0])
-            pts.append(o["center"] + np.array([c * l[0] - s * l[1], s * l[0] + c * l[1], l[2]]))
-    return np.array(pts)
 
 
 @pytest.fixture(scope="module")
@@ -298,19 +278,6 @@ def fworlds():
     assert fgeom.gate_desc["filling"].sum() == 2
     rg, ro, ws = _worlds(cfg, fgeom)
     return fgeom, rg, ro, ws
-
-
-def _gate_openings(gates, geom, n_per_gate=400, seed=3):
-    """States in and around every gate opening (the filling boxes), in world coordinates."""
-    rs = np.random.RandomState(seed)
-    out = []
-    for g in gates:
-        h = geom.gate_height[int(g[6])]
-        loc = rs.uniform([-0.3, -0.05, -0.3], [0.3, 0.05, 0.3], size=(n_per_gate, 3))
-        c, s = np.cos(g[5]), np.sin(g[5])
-        out.append(np.stack([g[0] + c * loc[:, 0] - s * loc[:, 1], g[1] + s * loc[:, 0] + c * loc[:, 1],
-                             h + loc[:, 2]], 1))
-    return np.vstack(out)
 
 
 @pytest.mark.parametrize("kernel", ["v5", "v4", "generic"])
