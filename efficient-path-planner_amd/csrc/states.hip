@@ -359,6 +359,21 @@ __device__ unsigned long long g_states_tl[kTlWaves][6];
     } while (0)
 #endif
 
+// The world's parameters reach the kernel by value (V5Args, filled on the host by
+// v5_args): nothing on a wave's way to its first load or to the staging barrier is
+// fetched through a pointer into device memory.  The arguments the first loads need
+// (stage_src = blob + off_aos, xyz, groups, stage_bytes) lead the list, scalars and
+// pointers only, so that the kernel-argument preload (Makefile, states.o) delivers
+// them in SGPRs at wave launch; the struct comes last (a leading struct disables the
+// preload).
+struct V5Args {
+    uint32_t lists_off, ids_off;  // list headers / list ids, bytes from the staged copy's start
+    uint32_t cls_off, cls_nz_off;  // the class table (bytes or u16) / the sparse classes' bytes
+    uint32_t nx, ny, nz;          // class cells per axis
+    float ox, oy, oz, ix, iy, iz;  // cell coordinate f = fmaf((float)p, i, o)
+    double rg, ro;                // inflate radii
+};
+
 // PREFETCH: groups per lane > 1 (the next group's loads overlap this one's work);
 // single-pass launches (e.g. 1M states on 256 CUs) drop the second buffer's registers.
 // SPL: states per lane and group (4: 96 B = six 16-B loads, 8: 192 B = twelve); one
@@ -366,11 +381,11 @@ __device__ unsigned long long g_states_tl[kTlWaves][6];
 // of the per-wave fixed costs (setup, staging, the exact path).
 // SC: staging chunks (16 B) per lane: enough for the staged bytes (launcher's choice).
 template <bool MINDIST, bool COMPACT, int BLOCK, bool PREFETCH, int SPL, bool C8, int SC>
-__global__ __launch_bounds__(BLOCK) void k_states_v5(const WorldView* __restrict__ wv,
-                                                     const double* xyz, int64_t groups, int64_t n,
-                                                     int can_pass, double md, uint8_t* __restrict__ valid,
+__global__ __launch_bounds__(BLOCK) void k_states_v5(const unsigned char* stage_src, const double* xyz,
+                                                     int64_t groups, uint32_t stage_bytes, int can_pass,
+                                                     int64_t n, double md, uint8_t* __restrict__ valid,
                                                      int32_t* __restrict__ compact_idx,
-                                                     unsigned long long* __restrict__ n_valid, uint32_t stage_bytes) {
+                                                     unsigned long long* __restrict__ n_valid, V5Args wa) {
     __shared__ WaveQueue5 queues[BLOCK / 64];
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_blob[];
     const int lane = threadIdx.x & 63;
@@ -381,8 +396,9 @@ __global__ __launch_bounds__(BLOCK) void k_states_v5(const WorldView* __restrict
     int64_t g = gfirst + threadIdx.x;
     constexpr int NV = 3 * SPL;  // doubles per group
     double va[NV], vb[NV];
-    // (no full group: loads read the WorldView instead, >= 96 bytes, ignored)
-    const double* xyzb = groups > 0 ? xyz : reinterpret_cast<const double*>(wv);
+    // (no full group: loads read the staging source instead, >= 16 * NV / 2 bytes
+    // (launch_states checks), ignored)
+    const double* xyzb = groups > 0 ? xyz : reinterpret_cast<const double*>(stage_src);
     auto load = [&](int64_t grp, double (&dst)[NV]) {
         grp = grp < groups ? grp : groups - 1;
         grp = grp < 0 ? 0 : grp;
@@ -408,9 +424,9 @@ __global__ __launch_bounds__(BLOCK) void k_states_v5(const WorldView* __restrict
     const uint32_t n16 = stage_bytes / 16u;  // >= 1 (the class table's sentinel)
 #if defined(__HIP_DEVICE_COMPILE__)  // global (not flat) loads: flat ones would also count lgkmcnt and force vmcnt(0)
     typedef const __attribute__((address_space(1))) u32x4* gptr_stage;
-    const gptr_stage ssrc = (gptr_stage)(wv->blob + wv->off_aos);
+    const gptr_stage ssrc = (gptr_stage)stage_src;
 #else
-    const u32x4* ssrc = reinterpret_cast<const u32x4*>(wv->blob + wv->off_aos);
+    const u32x4* ssrc = reinterpret_cast<const u32x4*>(stage_src);
 #endif
 #pragma unroll
     for (int i = 0; i < kStageChunks; ++i) {
@@ -424,16 +440,16 @@ __global__ __launch_bounds__(BLOCK) void k_states_v5(const WorldView* __restrict
         // (the launch allocates 16 spare bytes after the copy: the dummy slot)
         *reinterpret_cast<u32x4*>(lds_blob + 16u * (o < n16 ? o : n16)) = stg[i];
     }
-    const uint32_t lists_off = wv->off_lists - wv->off_aos, ids_off = wv->off_ids - wv->off_aos;
+    const uint32_t lists_off = wa.lists_off, ids_off = wa.ids_off;
     // the class table: bytes (C8, staged right after the lists) or u16
-    const unsigned char* cls_base = lds_blob + ((C8 ? wv->off_cls8 : wv->off_bitmap) - wv->off_aos);
-    [[maybe_unused]] const unsigned char* cls_nz = cls_base + ((wv->bm_words + 1u + 31u) >> 5) * 8u;  // (sparse classes)
+    const unsigned char* cls_base = lds_blob + wa.cls_off;
+    [[maybe_unused]] const unsigned char* cls_nz = lds_blob + wa.cls_nz_off;  // (sparse classes)
     const uint32_t* hdrs = reinterpret_cast<const uint32_t*>(lds_blob + lists_off);
     const uint16_t* ids_all = reinterpret_cast<const uint16_t*>(lds_blob + ids_off);
     const double* recs = reinterpret_cast<const double*>(lds_blob);
-    const float ox = wv->bofx, oy = wv->bofy, oz = wv->bofz, ix = wv->bix, iy = wv->biy, iz = wv->biz;
-    const uint32_t nx = (uint32_t)wv->bnx, ny = (uint32_t)wv->bny, nz = (uint32_t)wv->bnz;
-    const double rg = wv->r_gate, ro = wv->r_obst;
+    const float ox = wa.ox, oy = wa.oy, oz = wa.oz, ix = wa.ix, iy = wa.iy, iz = wa.iz;
+    const uint32_t nx = wa.nx, ny = wa.ny, nz = wa.nz;
+    const double rg = wa.rg, ro = wa.ro;
     __syncthreads();
     EPP_STL(1);
     auto cls_of = [&](double px, double py, double pz) -> uint32_t {
@@ -643,6 +659,22 @@ StatesKernel forced_kernel() {
 uint32_t v5_staged(const WorldView& w) {
     return (w.off_cls8 ? ((w.off_cls8 + w.cls8_bytes + 15u) & ~15u) : w.blob_bytes) - w.off_aos;
 }
+// The by-value world parameters of k_states_v5 (offsets relative to the staged copy)
+V5Args v5_args(const WorldView& w) {
+    V5Args a{};
+    a.lists_off = w.off_lists - w.off_aos;
+    a.ids_off = w.off_ids - w.off_aos;
+    a.cls_off = (w.off_cls8 ? w.off_cls8 : w.off_bitmap) - w.off_aos;
+    a.cls_nz_off = a.cls_off + ((w.bm_words + 1u + 31u) >> 5) * 8u;
+    a.nx = (uint32_t)w.bnx; a.ny = (uint32_t)w.bny; a.nz = (uint32_t)w.bnz;
+    a.ox = w.bofx; a.oy = w.bofy; a.oz = w.bofz;
+    a.ix = w.bix; a.iy = w.biy; a.iz = w.biz;
+    a.rg = w.r_gate; a.ro = w.r_obst;
+    return a;
+}
+// Launches without a full group (n < 4) aim their (ignored) state loads at the staging
+// source: it must hold the 96 bytes a lane loads.
+constexpr uint32_t kV5DummyBytes = 96;
 bool v5_fits(const WorldView& w) {
     const uint32_t sb = v5_staged(w);
     return sb <= kStageBudget && sb + 16u + queue5_bytes<1024>() <= 160u * 1024u;
@@ -703,7 +735,8 @@ epp_status launch_states(const WorldView& w, const WorldView* dw, const double* 
     const char* what = MINDIST ? "epp_check_states_mindist" : "epp_check_states";
     const StatesKernel want = forced_kernel();
     const bool x16 = (reinterpret_cast<uintptr_t>(xyz) & 15) == 0;
-    if (want == StatesKernel::V5 && v5_fits(w) && x16 && (reinterpret_cast<uintptr_t>(valid) & 3) == 0) {
+    if (want == StatesKernel::V5 && v5_fits(w) && x16 && (reinterpret_cast<uintptr_t>(valid) & 3) == 0 &&
+        (n >= 4 || w.blob_bytes - w.off_aos >= kV5DummyBytes)) {
 #ifdef EPP_V5_STAGECAP  // (diagnostics timing probes only: WRONG answers) stage at most this many bytes
         const uint32_t sb = std::min<uint32_t>(v5_staged(w), EPP_V5_STAGECAP);
 #else
@@ -715,11 +748,13 @@ epp_status launch_states(const WorldView& w, const WorldView* dw, const double* 
             sh.grid = (int)std::max<int64_t>(1, (sh.gN + 511) / 512);
         }
         const uint32_t dyn = sb + 16u;  // the staged world + the dummy slot of the copy
+        const unsigned char* src = w.blob + w.off_aos;
+        const V5Args wa = v5_args(w);
 #define EPP_LAUNCH_V5S(C, B, P, C8, SC)                                                                              \
     do {                                                                                                             \
         allow_lds(k_states_v5<MINDIST, C, B, P, 4, C8, SC>, queue5_bytes<B>());                                      \
-        hipLaunchKernelGGL((k_states_v5<MINDIST, C, B, P, 4, C8, SC>), dim3(sh.grid), dim3(B), dyn, st, dw, xyz, sh.gN, \
-                           n, can_pass, md, valid, compact_idx, nv, sb);                                             \
+        hipLaunchKernelGGL((k_states_v5<MINDIST, C, B, P, 4, C8, SC>), dim3(sh.grid), dim3(B), dyn, st, src, xyz,   \
+                           sh.gN, sb, can_pass, n, md, valid, compact_idx, nv, wa);                                  \
     } while (0)
         // staging chunks per lane: as many as the staged bytes need (1, 2 or 3), else half
         // the budget's or the whole budget's

@@ -1,7 +1,11 @@
 """Per-wave timeline of the headline kernel (k_states_v5, C2: 64 OBBs, 1M states): builds
 a diagnostics copy of libepp.so with -DEPP_STATES_TL into scripts/dbg/ (not the product),
 runs 200 launches, and prints percentiles of each wave's stamps relative to the launch's
-first stamp: staging barrier, data arrived + classified, exact path done, end."""
+first stamp: entry, staging barrier, data arrived + classified, exact path done, end; and
+each wave's own differences (entry -> barrier = the prologue as the wave lived it, without
+the dispatch ramp; barrier -> classified; classified -> exact done).
+python scripts/states_timeline.py [noexact] [lib.so]: with a library path, that diagnostics
+build is used as it is (e.g. the parent commit's, built elsewhere)."""
 import ctypes as C
 import os
 import subprocess
@@ -14,9 +18,12 @@ sys.path[:0] = [os.path.join(ROOT, "efficient-path-planner_amd")]
 from eppamd import capi, config, synth  # noqa: E402
 
 out = os.path.join(ROOT, "scripts", "dbg")
-variant = sys.argv[1] if len(sys.argv) > 1 else ""  # "" or "noexact" (-DEPP_STATES_NOEXACT: wrong answers)
-lib_path = os.path.join(out, f"libepp_stl{variant}.so")
+argv = sys.argv[1:]
+given = [a for a in argv if a.endswith(".so")]
+variant = "noexact" if "noexact" in argv else ""  # -DEPP_STATES_NOEXACT: wrong answers
+lib_path = os.path.abspath(given[0]) if given else os.path.join(out, f"libepp_stl{variant}.so")
 if not os.path.exists(lib_path):
+    assert not given, lib_path
     extra = "-DEPP_STATES_TL" + (" -DEPP_STATES_NOEXACT" if variant == "noexact" else "")
     subprocess.run(["make", "-s", "-j16", "-C", os.path.join(ROOT, "efficient-path-planner_amd"),
                     f"BUILD={out}/build_stl{variant}", f"LIB={lib_path}", f"EXTRA={extra}", lib_path], check=True)
@@ -43,12 +50,23 @@ for r in range(200):
         tl = np.zeros((waves, 6), np.uint64)
         capi.check(L.epp_dbg_states_tl(tl.ctypes.data, waves))
         rows.append(tl.astype(np.int64))
-for name, k in (("staging barrier", 1), ("classified", 2), ("exact done", 3), ("end", 4)):
-    v = np.concatenate([(t[:, k] - t[:, 0].min()) * 10 for t in rows]) / 1000.0  # us
-    print(f"{name:16s} p1 {np.percentile(v, 1):6.2f}  p10 {np.percentile(v, 10):6.2f}  p50 {np.percentile(v, 50):6.2f}"
+
+
+def line(name, v):
+    print(f"{name:24s} p1 {np.percentile(v, 1):6.2f}  p10 {np.percentile(v, 10):6.2f}  p50 {np.percentile(v, 50):6.2f}"
           f"  p90 {np.percentile(v, 90):6.2f}  p99 {np.percentile(v, 99):6.2f}  max {v.max():6.2f} us")
-v = np.concatenate([(t[:, 0] - t[:, 0].min()) * 10 for t in rows]) / 1000.0
-print(f"{'entry':16s} p50 {np.percentile(v, 50):6.2f} max {v.max():6.2f} us")
+
+
+print(f"{os.path.basename(lib_path)}: {len(rows)} launches x {waves} waves, us from the launch's first entry")
+for name, k in (("entry", 0), ("staging barrier", 1), ("classified", 2), ("exact done", 3), ("end", 4)):
+    line(name, np.concatenate([(t[:, k] - t[:, 0].min()) * 10 for t in rows]) / 1000.0)
+print("per wave (each wave's own stamps):")
+for name, a, b in (("entry -> barrier", 0, 1), ("barrier -> classified", 1, 2), ("classified -> exact done", 2, 3),
+                   ("entry -> end", 0, 4)):
+    line(name, np.concatenate([(t[:, b] - t[:, a]) * 10 for t in rows]) / 1000.0)
+# the waves that end the launch: the last 5 % by entry
+late = np.concatenate([((t[:, 1] - t[:, 0]) * 10)[t[:, 0] >= np.percentile(t[:, 0], 95)] for t in rows]) / 1000.0
+line("entry -> barrier, late 5%", late)
 ex = np.concatenate([(t[:, 3] - t[:, 2]) * 10 for t in rows]) / 1000.0
 print(f"exact path per wave: p50 {np.percentile(ex, 50):.2f} p90 {np.percentile(ex, 90):.2f} max {ex.max():.2f} us")
 nd = np.concatenate([(t[:, 5] >> 32) & 0xFFFF for t in rows])
