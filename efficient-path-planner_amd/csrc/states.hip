@@ -319,14 +319,14 @@ __global__ __launch_bounds__(kBlock4) void k_states_v4(const WorldView* __restri
 // workgroup while the first group's HBM loads are in flight.  Per state: class lookup
 // (LDS, ~15 VALU: the class grid's empty margin cells make a clamp do the bounds test)
 // -> ballot; a group with needy states queues them in the wave's LDS queue and, in the
-// common case (<= 64 needy states and <= 64 candidate pairs), tests each (state,
-// candidate) pair on its own lane with the hits returned by one ballot; otherwise each
+// common case (<= 64 needy states and <= 128 candidate pairs), tests each (state,
+// candidate) pair on its own lane (the pairs laid out by a lane permute and a max-scan, no
+// LDS round trip) with the hits returned by one ballot per 64 pairs; otherwise each
 // queued state walks its own list.  One 32-bit store writes a lane's four flags.
 // The per-state VALU count matters: at 1M states/launch the kernel's critical path is
 // the last-arriving data plus the VALU work behind it (PMC: SQ_INSTS_VALU).
 struct WaveQueue5 {
     double x[64], y[64], z[64];
-    uint32_t pair[128];  // segment heads of the (state, candidate) pairs
     uint32_t hdr[64];  // the queued states' list headers (start << 12 | count)
 };
 template <int BLOCK>
@@ -339,14 +339,33 @@ __device__ __forceinline__ uint32_t cell_axis5(double p, float off, float inv, u
     asm("v_cvt_i32_f32 %0, %1" : "=v"(i) : "v"(f));
     return min((uint32_t)i, nm1);  // negative -> huge -> last (empty) cell
 }
+// a * b + c on 24-bit operands (cells per axis <= 4096), b wave-uniform: one v_mad_u32_u24
+// (__umul24(a, b) + c becomes a 64-bit v_mad_u64_u32)
+__device__ __forceinline__ uint32_t mad_u24(uint32_t a, uint32_t b, uint32_t c) {
+    uint32_t r;
+    asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(b), "v"(c));
+    return r;
+}
+// The (state, candidate) pairs of a queue round are laid out over the lanes by a forward
+// lane permute (ds_permute_b32: no LDS memory is touched).  Lane i sends `data` to lane
+// `target` (mod 64); a lane that no lane targets receives 0.  Every lane of the wave
+// executes it (a lane outside EXEC would neither send nor receive); where several lanes
+// target one lane the callers make them send the same value, so the result does not depend
+// on which of them the hardware lets win.
+__device__ __forceinline__ uint32_t lane_scatter(uint32_t target, uint32_t data) {
+    return (uint32_t)__builtin_amdgcn_ds_permute((int)((target & 63u) << 2), (int)data);
+}
 
 // Per-wave timeline of k_states_v5 (diagnostics builds only: -DEPP_STATES_TL, see
 // scripts/states_timeline.py): lane 0 stamps s_memrealtime (100 MHz) at entry, after the
-// staging barrier, after the first group's classification (its data arrived), after its
-// exact path, at the end; plus HW_ID.
+// staging barrier, when the first group's state data have arrived (right behind an explicit
+// vmcnt(0) wait: single-pass instantiations only, a prefetching one would drain its next
+// group there and leaves the stamp 0), after that group's classification, after its exact
+// path, at the end; plus HW_ID.  Eight words per wave: stamps 0-5, HW_ID | counts, spare.
 #ifdef EPP_STATES_TL
 constexpr int kTlWaves = 1 << 16;
-__device__ unsigned long long g_states_tl[kTlWaves][6];
+constexpr int kTlWords = 8;
+__device__ unsigned long long g_states_tl[kTlWaves][kTlWords];
 #define EPP_STL(k)                                                                                  \
     do {                                                                                            \
         const int w_ = (int)((blockIdx.x * BLOCK + threadIdx.x) >> 6);                             \
@@ -380,8 +399,12 @@ struct V5Args {
 // flag store of SPL bytes.  More states per lane = fewer waves, i.e. fewer executions
 // of the per-wave fixed costs (setup, staging, the exact path).
 // SC: staging chunks (16 B) per lane: enough for the staged bytes (launcher's choice).
+// The single-pass 512-thread shape (the headline's) is held to five waves per SIMD's worth of
+// registers (96 VGPRs), as it was built before the lane-permute pair layout; no scratch
+// (tests/test_kernel_resources.py).
 template <bool MINDIST, bool COMPACT, int BLOCK, bool PREFETCH, int SPL, bool C8, int SC>
-__global__ __launch_bounds__(BLOCK) void k_states_v5(const unsigned char* stage_src, const double* xyz,
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(BLOCK == 512 && !PREFETCH ? 5 : BLOCK / 256)))
+void k_states_v5(const unsigned char* stage_src, const double* xyz,
                                                      int64_t groups, uint32_t stage_bytes, int can_pass,
                                                      int64_t n, double md, uint8_t* __restrict__ valid,
                                                      int32_t* __restrict__ compact_idx,
@@ -452,19 +475,48 @@ __global__ __launch_bounds__(BLOCK) void k_states_v5(const unsigned char* stage_
     const double rg = wa.rg, ro = wa.ro;
     __syncthreads();
     EPP_STL(1);
-    auto cls_of = [&](double px, double py, double pz) -> uint32_t {
+    auto cell_of = [&](double px, double py, double pz) -> uint32_t {
         const uint32_t cx = cell_axis5(px, ox, ix, nx - 1), cy = cell_axis5(py, oy, iy, ny - 1),
                        cz = cell_axis5(pz, oz, iz, nz - 1);
-        const uint32_t idx = __umul24(__umul24(cz, ny) + cy, nx) + cx;
+        return mad_u24(mad_u24(cz, ny, cy), nx, cx);
+    };
+    // Classes of N cells, batched and branch-free: all the first reads are issued, then all
+    // the second ones, so N lookups cost two LDS round trips (sparse bytes) or one, not
+    // 2 N.  occ[k] != 0: the class is not 0 — for sparse bytes that is the cell's occupancy
+    // bit, known one round trip before c[k].
+    // Sparse byte classes: per 32 cells one u64 [occupancy bits | occupied cells before this
+    // word], then the class bytes (all non-zero) of the occupied cells.  The class byte is
+    // read for every cell, occupied or not, and dropped for an unoccupied one.  There
+    // rank <= the number of occupied cells, so the read may land on the first byte after
+    // the class bytes, at cls_nz_off + occupied = cls_off + cls8_bytes <= stage_bytes
+    // (v5_staged rounds that end up to 16): inside the launch's stage_bytes + 16 bytes
+    // of dynamic LDS (launch_states, dyn), at worst in the staging copy's dummy slot.
+    auto classes_of = [&](const auto& idx, auto& c, auto& occ) {
+        constexpr int N = (int)(sizeof(idx) / sizeof(idx[0]));
 #ifndef EPP_V5_DENSE_CLS
-        if (C8) {  // sparse byte classes: the occupancy word, then (occupied cells) the class byte
-            const uint64_t wd = reinterpret_cast<const uint64_t*>(cls_base)[idx >> 5];
-            const uint32_t m = (uint32_t)wd, sh = idx & 31u;
-            const uint32_t rank = (uint32_t)(wd >> 32) + (uint32_t)__popc(m & ((1u << sh) - 1u));
-            return ((m >> sh) & 1u) ? (uint32_t)cls_nz[rank] : 0u;
+        if (C8) {
+            uint64_t wd[N];
+            uint32_t rank[N];
+#pragma unroll
+            for (int k = 0; k < N; ++k) wd[k] = reinterpret_cast<const uint64_t*>(cls_base)[idx[k] >> 5];
+#pragma unroll
+            for (int k = 0; k < N; ++k) {
+                const uint32_t m = (uint32_t)wd[k], sh = idx[k] & 31u;
+                rank[k] = (uint32_t)(wd[k] >> 32) + (uint32_t)__popc(m & ((1u << sh) - 1u));
+                occ[k] = (m >> sh) & 1u;
+            }
+#pragma unroll
+            for (int k = 0; k < N; ++k) c[k] = (uint32_t)cls_nz[rank[k]];
+#pragma unroll
+            for (int k = 0; k < N; ++k) c[k] = occ[k] ? c[k] : 0u;
+            return;
         }
 #endif
-        return C8 ? (uint32_t)cls_base[idx] : (uint32_t)reinterpret_cast<const uint16_t*>(cls_base)[idx];
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            c[k] = C8 ? (uint32_t)cls_base[idx[k]] : (uint32_t)reinterpret_cast<const uint16_t*>(cls_base)[idx[k]];
+            occ[k] = c[k];
+        }
     };
 #ifdef EPP_STATES_TL
     uint32_t tl_needy = 0, tl_pairs = 0;  // (diagnostics) queued states and pairs
@@ -475,16 +527,26 @@ __global__ __launch_bounds__(BLOCK) void k_states_v5(const unsigned char* stage_
         bool needy[SPL];
         unsigned long long b[SPL];
         uint32_t base[SPL], total = 0;
+#ifdef EPP_STATES_TL
+        if (!PREFETCH) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            EPP_STL(2);
+        }
+#endif
+        uint32_t cell[SPL], occ[SPL];
 #pragma unroll
-        for (int k = 0; k < SPL; ++k) c[k] = cls_of(v[3 * k], v[3 * k + 1], v[3 * k + 2]);
+        for (int k = 0; k < SPL; ++k) cell[k] = cell_of(v[3 * k], v[3 * k + 1], v[3 * k + 2]);
+        classes_of(cell, c, occ);
+        const uint32_t live_bits = live ? ~0u : 0u;
 #pragma unroll
         for (int k = 0; k < SPL; ++k) {
-            needy[k] = live & (c[k] != 0u);
-            b[k] = __ballot(needy[k]);
+            // (one compare: its lane mask is the ballot)
+            needy[k] = (occ[k] & live_bits) != 0u;
+            b[k] = __builtin_amdgcn_ballot_w64(needy[k]);
             base[k] = total;
             total += (uint32_t)__popcll(b[k]);
         }
-        EPP_STL(2);
+        EPP_STL(3);
         // the needy states' list headers, read now (one LDS round trip for all four,
         // overlapping the ballot arithmetic) and queued with the state
         uint32_t hd[SPL];
@@ -528,26 +590,43 @@ __global__ __launch_bounds__(BLOCK) void k_states_v5(const unsigned char* stage_
                 bool hit_e = false;
                 if (ptot <= 128u) {
                     // one (state, candidate) pair per lane and round (two rounds at most):
-                    // pair q finds its state as the max-scan of segment heads (state e
-                    // marks position poff_e); hits come back by ballot
-                    qu->pair[lane] = 0u;
-                    qu->pair[64 + lane] = 0u;
-                    if (act) qu->pair[poff] = (uint32_t)lane;  // cnt >= 1 for queued states
-                    wave_lds_sync();
-                    const uint32_t e0 = dpp_incl_max(qu->pair[lane]);
-                    auto test = [&](uint32_t e, uint32_t q) {
-                        const uint32_t pe = (uint32_t)__shfl((int)poff, (int)e, 64);
-                        const uint32_t fe = (uint32_t)__shfl((int)first, (int)e, 64);
-                        return q < ptot && rec_hit<MINDIST>(recs + (size_t)ids_all[fe + q - pe] * kRecDoubles, rg, ro,
-                                                            qu->x[e], qu->y[e], qu->z[e], can_pass != 0, md);
+                    // state e marks pair position poff_e, the head of its segment (distinct
+                    // positions: cnt >= 1 for queued states), with
+                    //   (e + 1) << 21 | (first_e - poff_e + 128)
+                    // (first: 20 bits, poff <= 128, so the low field is < 2^21 and not
+                    // negative; e + 1 <= 64), sent there by one lane_scatter per 64 positions.
+                    // The max-scan of the heads hands pair q its state (the high field
+                    // orders the heads) and, in the low field, its id's index less q - 128.
+                    // Hits come back by ballot.
+                    // Lanes with no head among the 64 positions repeat a head that is: lane
+                    // 0's (position 0) for the first 64, the last queued state's for the
+                    // second 64 (poff ascends: if its head is not there, no head is, and
+                    // everyone sends 0).
+                    uint32_t ln = (uint32_t)lane;
+                    asm volatile("" : "+v"(ln));  // (keeps (lane + 1) << 21 from living in a register of its own)
+                    const uint32_t head = (ln << 21) + (first - poff + ((1u << 21) + 128u));
+                    const bool own0 = act & (poff < 64u);
+                    const uint32_t head0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)head);
+                    const uint32_t h0 = dpp_incl_max(lane_scatter(own0 ? poff : 0u, own0 ? head : head0));
+                    auto test = [&](uint32_t h, uint32_t q) {
+                        const uint32_t e = (h >> 21) - 1u;  // (h != 0: position 0 is a head)
+                        return q < ptot &&
+                               rec_hit<MINDIST>(recs + (size_t)ids_all[(h & 0x1FFFFFu) + q - 128u] * kRecDoubles, rg, ro,
+                                                qu->x[e], qu->y[e], qu->z[e], can_pass != 0, md);
                     };
-                    const unsigned long long m0 = __ballot(test(e0, (uint32_t)lane));
                     unsigned long long m1 = 0ull;
+                    uint32_t h1 = 0u;
                     if (ptot > 64u) {  // wave-uniform
-                        const uint32_t carry = (uint32_t)__builtin_amdgcn_readlane((int)e0, 63);
-                        const uint32_t e1 = max(dpp_incl_max(qu->pair[64 + lane]), carry);
-                        m1 = __ballot(test(e1, 64u + (uint32_t)lane));
+                        const uint32_t plast = (uint32_t)__builtin_amdgcn_readlane((int)poff, (int)(tq - 1u));
+                        const uint32_t hlast = (uint32_t)__builtin_amdgcn_readlane((int)head, (int)(tq - 1u));
+                        const bool own1 = act & (poff >= 64u);
+                        const uint32_t carry = (uint32_t)__builtin_amdgcn_readlane((int)h0, 63);
+                        h1 = max(dpp_incl_max(lane_scatter(own1 ? poff : plast,  // (mod 64)
+                                                           own1 ? head : (plast >= 64u ? hlast : 0u))),
+                                 carry);
                     }
+                    const unsigned long long m0 = __builtin_amdgcn_ballot_w64(test(h0, (uint32_t)lane));
+                    if (ptot > 64u) m1 = __builtin_amdgcn_ballot_w64(test(h1, 64u + (uint32_t)lane));
                     // any hit among this state's pairs [poff, poff + cnt) of the 128-bit mask
                     auto bits = [](unsigned long long m, uint32_t from, uint32_t len) {
                         const unsigned long long msk = len >= 64u ? ~0ull : ((1ull << len) - 1ull);
@@ -566,7 +645,7 @@ __global__ __launch_bounds__(BLOCK) void k_states_v5(const unsigned char* stage_
                                                   md);
                 }
                 // back to the owners: state slot r0 + e lives on lane e
-                const unsigned long long hm = __ballot(hit_e);
+                const unsigned long long hm = __builtin_amdgcn_ballot_w64(hit_e);
 #pragma unroll
                 for (int k = 0; k < SPL; ++k) {
                     const uint32_t slot = pos[k] - r0;
@@ -575,7 +654,7 @@ __global__ __launch_bounds__(BLOCK) void k_states_v5(const unsigned char* stage_
                 wave_lds_sync();  // the queue is rewritten next
             }
         }
-        EPP_STL(3);
+        EPP_STL(4);
         const uint32_t fl = live ? (~hits & ((1u << SPL) - 1u)) : 0u;  // bit k: state SPL gg + k valid
         if (live) {
             if (SPL == 4) {
@@ -618,22 +697,24 @@ __global__ __launch_bounds__(BLOCK) void k_states_v5(const unsigned char* stage_
         }
     }
 #ifdef EPP_STATES_TL
-    EPP_STL(4);
+    EPP_STL(5);
     if (lane == 0) {
         unsigned hw;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
         const int w_ = (int)((blockIdx.x * BLOCK + threadIdx.x) >> 6);
         if (w_ < kTlWaves)
-            g_states_tl[w_][5] = hw | ((unsigned long long)min(tl_needy, 65535u) << 32) |
+            g_states_tl[w_][6] = hw | ((unsigned long long)min(tl_needy, 65535u) << 32) |
                                  ((unsigned long long)min(tl_pairs, 65535u) << 48);
     }
 #endif
     if (blockIdx.x == 0 && threadIdx.x < (int)(n - SPL * groups)) {  // tail: the last n % SPL states
         const int64_t i = SPL * groups + threadIdx.x;
         const double px = xyz[3 * i], py = xyz[3 * i + 1], pz = xyz[3 * i + 2];
-        const uint32_t c = cls_of(px, py, pz);
-        const bool ok = !(c != 0u && states_exact_rec<MINDIST>(lds_blob, lists_off, ids_off, rg, ro, px, py, pz, c,
-                                                               can_pass, md));
+        const uint32_t cell[1] = {cell_of(px, py, pz)};
+        uint32_t c[1], occ[1];
+        classes_of(cell, c, occ);
+        const bool ok = !(occ[0] != 0u && states_exact_rec<MINDIST>(lds_blob, lists_off, ids_off, rg, ro, px, py, pz, c[0],
+                                                              can_pass, md));
         valid[i] = ok ? 1 : 0;
         if (COMPACT && ok) compact_idx[atomicAdd(n_valid, 1ull)] = (int32_t)i;
     }
@@ -868,7 +949,7 @@ epp_status epp_check_states(const epp_world* world, const double* xyz, int64_t n
 #ifdef EPP_STATES_TL
 // diagnostics builds only: the per-wave timeline of the last k_states_v5 launch
 epp_status epp_dbg_states_tl(unsigned long long* out, int64_t waves) {
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_states_tl), (size_t)std::min<int64_t>(waves, kTlWaves) * 48) == hipSuccess
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_states_tl), (size_t)std::min<int64_t>(waves, kTlWaves) * kTlWords * 8) == hipSuccess
                ? EPP_OK
                : EPP_ERR_HIP;
 }

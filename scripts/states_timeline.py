@@ -1,9 +1,10 @@
 """Per-wave timeline of the headline kernel (k_states_v5, C2: 64 OBBs, 1M states): builds
 a diagnostics copy of libepp.so with -DEPP_STATES_TL into scripts/dbg/ (not the product),
 runs 200 launches, and prints percentiles of each wave's stamps relative to the launch's
-first stamp: entry, staging barrier, data arrived + classified, exact path done, end; and
-each wave's own differences (entry -> barrier = the prologue as the wave lived it, without
-the dispatch ramp; barrier -> classified; classified -> exact done).
+first stamp: entry, staging barrier, state data arrived, classified, exact path done, end;
+and each wave's own differences (entry -> barrier = the prologue as the wave lived it,
+without the dispatch ramp; barrier -> data arrived; data arrived -> classified; classified
+-> exact done).  Eight words per wave (states.hip, kTlWords).
 python scripts/states_timeline.py [noexact] [lib.so]: with a library path, that diagnostics
 build is used as it is (e.g. the parent commit's, built elsewhere)."""
 import ctypes as C
@@ -47,7 +48,7 @@ for r in range(200):
     w.check_states_dev(d.ptr + (r % NB) * N * 24, N, 0, dv.ptr)
     if r >= 150 and r % 5 == 0:
         capi.sync()
-        tl = np.zeros((waves, 6), np.uint64)
+        tl = np.zeros((waves, 8), np.uint64)
         capi.check(L.epp_dbg_states_tl(tl.ctypes.data, waves))
         rows.append(tl.astype(np.int64))
 
@@ -58,19 +59,20 @@ def line(name, v):
 
 
 print(f"{os.path.basename(lib_path)}: {len(rows)} launches x {waves} waves, us from the launch's first entry")
-for name, k in (("entry", 0), ("staging barrier", 1), ("classified", 2), ("exact done", 3), ("end", 4)):
+for name, k in (("entry", 0), ("staging barrier", 1), ("data arrived", 2), ("classified", 3), ("exact done", 4),
+                ("end", 5)):
     line(name, np.concatenate([(t[:, k] - t[:, 0].min()) * 10 for t in rows]) / 1000.0)
 print("per wave (each wave's own stamps):")
-for name, a, b in (("entry -> barrier", 0, 1), ("barrier -> classified", 1, 2), ("classified -> exact done", 2, 3),
-                   ("entry -> end", 0, 4)):
+for name, a, b in (("entry -> barrier", 0, 1), ("barrier -> data arrived", 1, 2), ("data arrived -> classified", 2, 3),
+                   ("classified -> exact done", 3, 4), ("entry -> end", 0, 5)):
     line(name, np.concatenate([(t[:, b] - t[:, a]) * 10 for t in rows]) / 1000.0)
 # the waves that end the launch: the last 5 % by entry
 late = np.concatenate([((t[:, 1] - t[:, 0]) * 10)[t[:, 0] >= np.percentile(t[:, 0], 95)] for t in rows]) / 1000.0
 line("entry -> barrier, late 5%", late)
-ex = np.concatenate([(t[:, 3] - t[:, 2]) * 10 for t in rows]) / 1000.0
+ex = np.concatenate([(t[:, 4] - t[:, 3]) * 10 for t in rows]) / 1000.0
 print(f"exact path per wave: p50 {np.percentile(ex, 50):.2f} p90 {np.percentile(ex, 90):.2f} max {ex.max():.2f} us")
-nd = np.concatenate([(t[:, 5] >> 32) & 0xFFFF for t in rows])
-pr = np.concatenate([(t[:, 5] >> 48) & 0xFFFF for t in rows])
+nd = np.concatenate([(t[:, 6] >> 32) & 0xFFFF for t in rows])
+pr = np.concatenate([(t[:, 6] >> 48) & 0xFFFF for t in rows])
 print(f"queued states per wave: p50 {np.percentile(nd, 50):.0f} p90 {np.percentile(nd, 90):.0f} max {nd.max()}"
       f"; pairs per wave: p50 {np.percentile(pr, 50):.0f} p90 {np.percentile(pr, 90):.0f} max {pr.max()}"
       f"; > 64 pairs: {np.mean(pr > 64):.2f}, > 128: {np.mean(pr > 128):.3f}")
