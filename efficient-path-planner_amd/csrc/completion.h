@@ -1,6 +1,6 @@
 // completion.h — the completion slots of the synchronous latency paths, both halves (the
 // small state / ray checks of small.hip, the refit kernels of minsnap.hip, k_pb_emit of
-// planner.hip and their hosts).  A kernel's workgroups write their results into pinned host
+// plan_batch.hip and their hosts).  A kernel's workgroups write their results into pinned host
 // memory and then each publishes the call's sequence number in its own pinned slot
 // (publish_done); the host polls the slots (wait_done) instead of synchronising the stream.
 // Sequence numbers come from next_seq (never 0) and the slots are zeroed when their pinned

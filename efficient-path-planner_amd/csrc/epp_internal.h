@@ -51,15 +51,7 @@ namespace epp {
 epp_status generate_trajectory_into(const double* wp, int32_t n_wp, const double* times, double v_max,
                                     double a_max, double dt, double t0, const double v0[3], const double a0[3],
                                     double* (*alloc)(void*, int64_t), void* ctx, int64_t* n_rows);
-// The planner's pair of epp_sample_uniform + epp_compact_states_ws without the compaction's
-// separate clearing launch: the sampler also zeroes the workspace's status words
-// (clr_bytes: epp_compact_workspace_size), and the compaction that follows on the same
-// stream trusts them to be zero.
-epp_status sample_uniform_and_clear(uint64_t seed, const double lo[3], const double hi[3], int64_t n, double* xyz,
-                                    void* clr, uint64_t clr_bytes, void* stream);
-epp_status compact_states_cleared(const double* xyz, const uint8_t* valid, int64_t n, double* out, int64_t* n_out,
-                                  void* ws, uint64_t ws_bytes, void* stream);
-// The same with the C5 online step's A11 check fused into the launch (chk != NULL): the
+// generate_trajectory_into with the C5 online step's A11 check fused into the launch (chk != NULL): the
 // minDistance flags of chk->n points (host array) against chk->world, written to
 // chk->valid, by extra workgroups of the refit's kernel (k_check_refit).  The check must be
 // small (<= kSmallStates points, <= kSmallMaxObbs OBBs), else EPP_ERR_UNSUPPORTED.
@@ -103,24 +95,12 @@ epp_status check_knn_motions_masked(const epp_world* world, const double* nodes,
 // the masked table as u16, 0xFFFF for no edge (node counts <= 65535).
 epp_status mask_edges_count_acc(int32_t* nbr, const uint8_t* valid, int64_t m, int32_t target, int64_t* count,
                                 void* stream, uint16_t* out16 = nullptr);
-// The planner's row-restricted search.  pack_ellipse_rows: the rows of the int32 k-NN table
-// `tab` (n <= 65535 nodes x k) whose node x has |x - s| + |x - g| <= bound (widened by 1e-9
-// relative + 1e-9 m), packed: ids32 / ids16[slot] = node, rows32[slot * k ..] = its row,
-// *count += the rows found (slots >= cap are not written).
-epp_status pack_ellipse_rows(const double* nodes, const int32_t* tab, int32_t n, int32_t k, const double s[3],
-                             const double g[3], double bound, int32_t cap, int32_t* ids32, uint16_t* ids16,
-                             int32_t* rows32, int64_t* count, void* stream);
-// epp_knn_ws_box (max_dist 0) whose rows are exact for every node of that ellipsoid (the
-// grid as usual, then those nodes' rows alone, one wave each; other rows: unspecified).
 // The reverse edges of the masked k-NN table nbr (n x k, -1: none) as a CSR: roff (n + 1)
 // and radj (the sources of every node's in-edges, ascending; radj16, if given, the same as
 // u16); cnt / fill: n-int workspaces.  (PathPlanner's symmetrised search.)
 epp_status reverse_csr(const int32_t* nbr, int32_t n, int32_t k, int32_t* cnt, int32_t* fill, int32_t* roff,
                        int32_t* radj, uint16_t* radj16, void* stream);
-epp_status knn_ws_box_ellipse(const double* nodes, int32_t n, int32_t k, const double lo[3], const double hi[3],
-                              const double s[3], const double g[3], double bound, int32_t* nbr, void* ws,
-                              uint64_t ws_bytes, void* stream);
-// check_knn_motions_masked over the packed rows: rows32 (cap rows x k, row r = node
+// check_knn_motions_masked over the packed rows of the planner's row-restricted search: rows32 (cap rows x k, row r = node
 // ids32[r]), rows r < min(*rows_n, cap) only; EPP_ERR_UNSUPPORTED for worlds without tile
 // tables.  count == nullptr: the mask and out16 only (out16 = the entry's low 16 bits).
 // marks (optional): its mark / pkept / pgoal / ns_log / nprob fields (the planner batch).
@@ -135,7 +115,7 @@ epp_status check_knn_motions_rows(const epp_world* world, const double* nodes, i
 bool knn_motions_rows_supported(const epp_world* world);
 
 // ---- the batched planner (PathPlanner::planPaths): a batch of gate-to-gate problems, one
-// launch per device stage with blockIdx.y = the problem (planner.hip, plan_batch_launch).
+// launch per device stage with blockIdx.y = the problem (plan_batch.hip, plan_batch_launch).
 // Stages: sample -> state check -> ordered compaction (start, goal, valid samples) -> the
 // nodes inside each problem's grid ellipsoid |x - s| + |x - g| <= gbound into a small
 // k-NN grid, those inside the row ellipsoid (<= bound) listed as queries -> their exact
@@ -241,7 +221,7 @@ struct WorldView {
     uint32_t bm_words;        // index of the zero sentinel class
     uint32_t off_cls8;        // the same classes as bytes (0: more than 255 lists, none) --
                               // sparse: u64 [occupancy | rank] per 32 cells, then the
-                              // nonzero cells' bytes (world_index.cpp; dense with -DEPP_V5_DENSE_CLS)
+                              // nonzero cells' bytes (world_index.cpp)
     uint32_t cls8_bytes;      // bytes of that structure
     int32_t bnx, bny, bnz;    // cells per axis
     float bofx, bofy, bofz;   // offset: cell coordinate f = fmaf((float)p, bi, bof)

@@ -493,7 +493,6 @@ void k_states_v5(const unsigned char* stage_src, const double* xyz,
     // of dynamic LDS (launch_states, dyn), at worst in the staging copy's dummy slot.
     auto classes_of = [&](const auto& idx, auto& c, auto& occ) {
         constexpr int N = (int)(sizeof(idx) / sizeof(idx[0]));
-#ifndef EPP_V5_DENSE_CLS
         if (C8) {
             uint64_t wd[N];
             uint32_t rank[N];
@@ -511,10 +510,9 @@ void k_states_v5(const unsigned char* stage_src, const double* xyz,
             for (int k = 0; k < N; ++k) c[k] = occ[k] ? c[k] : 0u;
             return;
         }
-#endif
 #pragma unroll
         for (int k = 0; k < N; ++k) {
-            c[k] = C8 ? (uint32_t)cls_base[idx[k]] : (uint32_t)reinterpret_cast<const uint16_t*>(cls_base)[idx[k]];
+            c[k] = (uint32_t)reinterpret_cast<const uint16_t*>(cls_base)[idx[k]];  // (u16 classes)
             occ[k] = c[k];
         }
     };
@@ -818,11 +816,7 @@ epp_status launch_states(const WorldView& w, const WorldView* dw, const double* 
     const bool x16 = (reinterpret_cast<uintptr_t>(xyz) & 15) == 0;
     if (want == StatesKernel::V5 && v5_fits(w) && x16 && (reinterpret_cast<uintptr_t>(valid) & 3) == 0 &&
         (n >= 4 || w.blob_bytes - w.off_aos >= kV5DummyBytes)) {
-#ifdef EPP_V5_STAGECAP  // (diagnostics timing probes only: WRONG answers) stage at most this many bytes
-        const uint32_t sb = std::min<uint32_t>(v5_staged(w), EPP_V5_STAGECAP);
-#else
         const uint32_t sb = v5_staged(w);
-#endif
         V5Shape sh = v5_shape(n, sb);
         if (sh.bs == 256 && compact_idx) {  // (the 256-thread shape is instantiated without compaction)
             sh.bs = 512;

@@ -375,7 +375,7 @@ bool build_blob(HostWorld& hw, const epp_obb* obbs, int n) {
     const size_t off_lists = align16(off_aos + aos.size() * sizeof(double));
     const size_t off_ids = off_lists + hdr.size() * 4;
     // byte classes (k_states_v5 stages them instead of the u16 table) when the lists fit.
-    // Sparse form (the default; -DEPP_V5_DENSE_CLS: one byte per cell): per 32 cells one u64
+    // Sparse form: per 32 cells one u64
     // [occupancy bits | nonzero cells before this word], then the class bytes of the nonzero
     // cells in cell order -- 0.25 B per cell plus ~1 B per occupied cell (C2: 7 KB instead of
     // 18.5 KB staged by every workgroup).
@@ -383,7 +383,6 @@ bool build_blob(HostWorld& hw, const epp_obb* obbs, int n) {
     const size_t off_c8 = align16(off_ids + flat.size() * 2);
     std::vector<uint64_t> cwords;
     std::vector<uint8_t> cnz;
-#ifndef EPP_V5_DENSE_CLS
     if (c8) {
         cwords.assign((cls.size() + 31) / 32, 0ull);
         for (size_t w = 0; w < cwords.size(); ++w) {
@@ -398,9 +397,6 @@ bool build_blob(HostWorld& hw, const epp_obb* obbs, int n) {
         }
     }
     const size_t c8_bytes = c8 ? cwords.size() * 8 + cnz.size() : 0;
-#else
-    const size_t c8_bytes = c8 ? cls.size() : 0;
-#endif
     const size_t off_bm = c8 ? align16(off_c8 + c8_bytes) : off_c8;
     // ---- motion tile filter (k_motions_v5) ------------------------------------------
     // The smallest row width W (words of OBB bits), then the fewest tiles per axis T,
@@ -526,15 +522,10 @@ bool build_blob(HostWorld& hw, const epp_obb* obbs, int n) {
     std::memcpy(b + off_bm, cls.data(), cls.size() * 2);
     if (!slab.empty()) std::memcpy(b + off_slab, slab.data(), slab.size() * 4);
     v.off_slab = (uint32_t)off_slab;
-#ifndef EPP_V5_DENSE_CLS
     if (c8) {
         std::memcpy(b + off_c8, cwords.data(), cwords.size() * 8);
         if (!cnz.empty()) std::memcpy(b + off_c8 + cwords.size() * 8, cnz.data(), cnz.size());
     }
-#else
-    if (c8)
-        for (size_t c = 0; c < cls.size(); ++c) b[off_c8 + c] = (char)(uint8_t)cls[c];
-#endif
     v.off_cls8 = c8 ? (uint32_t)off_c8 : 0u;
     v.cls8_bytes = (uint32_t)c8_bytes;
     v.off_lists = (uint32_t)off_lists;
@@ -925,15 +916,11 @@ extern "C" int64_t epp_dbg_check_sparse_classes(const epp_obb* obbs, int32_t n, 
     const unsigned char* nz = base + ((v.bm_words + 1u + 31u) >> 5) * 8u;
     int64_t bad = 0;
     for (uint32_t idx = 0; idx <= v.bm_words; ++idx) {
-#ifndef EPP_V5_DENSE_CLS
         uint64_t wd;
         std::memcpy(&wd, base + (size_t)(idx >> 5) * 8, 8);
         const uint32_t m = (uint32_t)wd, sh = idx & 31u;
         const uint32_t rank = (uint32_t)(wd >> 32) + (uint32_t)__builtin_popcount(m & ((1u << sh) - 1u));
         const uint32_t c = ((m >> sh) & 1u) ? (uint32_t)nz[rank] : 0u;
-#else
-        const uint32_t c = base[idx];
-#endif
         bad += c != (uint32_t)cls[idx];
     }
     return bad;

@@ -54,7 +54,7 @@ def main():
         capi.check(L.epp_stream_sync(st))
         tab = d_k.download(np.int32, n * k).reshape(n, k)
         same = bool(np.array_equal(tab, ref))
-        # the workspace starts with the grid parameters (struct KnnGrid, planner.hip):
+        # the workspace starts with the grid parameters (struct KnnGrid, knn_grid.h):
         # lo[3], h, inv_h (f64), dims[3], ncell, next, nretry, why[4] (i32)
         hdr = d_ws.download(np.uint8, 80)
         dims = hdr[40:52].view(np.int32)
