@@ -1490,6 +1490,80 @@ bool PathPlanner::checkTrajectoryValidityAndGenerate(const Matrix& traj, double 
     return true;
 }
 
+bool PathPlanner::checkCandidateTrajectories(const std::vector<std::vector<Vec3>>& sets, double v_max, double a_max,
+                                             double dt, double minDistance, std::vector<long>& firstInvalidRow,
+                                             std::vector<double>* firstInvalidTime) const {
+    for (const auto& s : sets)
+        if (s.size() < 2) throw std::invalid_argument("At least two waypoints are required");
+    const size_t n = sets.size();
+    firstInvalidRow.assign(n, -1);
+    if (firstInvalidTime) firstInvalidTime->assign(n, -1.0);
+    if (n == 0) return true;
+    // host image of the upload: [waypoints | offsets]; device block: [wp | T | coeffs |
+    // first_time | first_invalid | offsets | status]
+    size_t total = 0;
+    for (const auto& s : sets) total += s.size();
+    const size_t nseg = total - n;
+    std::vector<double> wp(total * 3);
+    std::vector<int32_t> off(n + 1, 0);
+    size_t w = 0;
+    for (size_t k = 0; k < n; ++k) {
+        for (const Vec3& p : sets[k]) {
+            wp[3 * w] = p.x;
+            wp[3 * w + 1] = p.y;
+            wp[3 * w + 2] = p.z;
+            ++w;
+        }
+        off[k + 1] = (int32_t)w;
+    }
+    struct Dev {  // released on every way out
+        void* buf = nullptr;
+        void* st = nullptr;
+        ~Dev() {
+            if (st) (void)epp_stream_destroy(st);
+            if (buf) (void)epp_free(buf);
+        }
+    } d;
+    auto need = [](epp_status rc) {
+        if (rc == EPP_ERR_INVALID_ARGUMENT) throw std::invalid_argument(epp_last_error());
+        if (rc != EPP_OK) throw std::runtime_error(std::string("checkCandidateTrajectories: ") + epp_last_error());
+    };
+    auto after = [](size_t o, size_t b) { return (o + b + 255) & ~(size_t)255; };  // 256-B aligned parts
+    const size_t o_wp = 0, o_T = after(o_wp, total * 24), o_C = after(o_T, nseg * 8), o_ft = after(o_C, nseg * 240),
+                 o_fi = after(o_ft, n * 8), o_off = after(o_fi, n * 8), o_st = after(o_off, (n + 1) * 4),
+                 bytes = after(o_st, n * 4);
+    need(epp_malloc(&d.buf, bytes));
+    need(epp_stream_create(&d.st));
+    char* base = static_cast<char*>(d.buf);
+    need(epp_memcpy_h2d_async(base + o_wp, wp.data(), total * 24, d.st));
+    need(epp_memcpy_h2d_async(base + o_off, off.data(), (n + 1) * 4, d.st));
+    double* d_T = reinterpret_cast<double*>(base + o_T);
+    double* d_C = reinterpret_cast<double*>(base + o_C);
+    const int32_t* d_off = reinterpret_cast<const int32_t*>(base + o_off);
+    need(epp_minsnap_batch(reinterpret_cast<const double*>(base + o_wp), d_off, (int32_t)n, v_max, a_max, nullptr,
+                           nullptr, d_T, d_C, reinterpret_cast<int32_t*>(base + o_st), d.st));
+    need(epp_traj_check_batch(worldPtr->device(), d_T, d_C, d_off, (int32_t)n, dt, minDistance,
+                              reinterpret_cast<int64_t*>(base + o_fi), reinterpret_cast<double*>(base + o_ft), d.st));
+    std::vector<int32_t> status(n);
+    std::vector<int64_t> rows(n);
+    std::vector<double> times(n);
+    need(epp_memcpy_d2h_async(status.data(), base + o_st, n * 4, d.st));
+    need(epp_memcpy_d2h_async(rows.data(), base + o_fi, n * 8, d.st));
+    need(epp_memcpy_d2h_async(times.data(), base + o_ft, n * 8, d.st));
+    need(epp_stream_sync(d.st));
+    for (size_t k = 0; k < n; ++k)
+        if (status[k] != 0)
+            throw std::runtime_error("generateTrajectory: the fit of waypoint set " + std::to_string(k) +
+                                     " failed (status " + std::to_string(status[k]) + ")");
+    bool all = true;
+    for (size_t k = 0; k < n; ++k) {
+        firstInvalidRow[k] = (long)rows[k];
+        all = all && rows[k] < 0;
+    }
+    if (firstInvalidTime) *firstInvalidTime = times;
+    return all;
+}
+
 bool PathPlanner::checkTrajectoryValidityOn(const World& world, const Matrix& traj, double minDistance) {
     if (traj.rows == 0) return true;
     std::vector<double> xyz(traj.rows * 3);

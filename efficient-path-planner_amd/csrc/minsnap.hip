@@ -33,6 +33,7 @@
 #include "minsnap_consts.h"
 #include "pinned_buf.h"
 #include "small_body.h"
+#include "traj_sample.h"
 
 namespace epp {
 namespace {
@@ -540,69 +541,6 @@ __global__ __launch_bounds__(BLOCK) void k_minsnap(const double* __restrict__ wp
     if (threadIdx.x == 0 && status) status[track] = st;
 }
 
-constexpr int kRowChunk = 512;  // samples per k_sample_rows round
-
-// Trajectory::evaluateRange control flow — src/trajectory.cpp:81-141.
-struct RangeIter {
-    const double* T;
-    int M, i;
-    double t_end, acc, tis, Ti;  // Ti = T[i], kept in a register (one LDS read per segment)
-    __host__ __device__ void init(const double* T_, int M_) {
-        T = T_;
-        M = M_;
-        t_end = 0.0;  // max_time_ += segment.getTime()  trajectory.h:63-70
-        for (int k = 0; k < M; ++k) t_end = t_end + T[k];
-        acc = 0.0;
-        for (i = 0; i < M; ++i) {  // t_start = 0
-            acc = acc + T[i];
-            if (acc > 0.0) break;
-        }
-        if (i >= M) i = M - 1;
-        acc = acc - T[i];
-        tis = 0.0 - acc;
-        Ti = T[i];
-    }
-    // Advances to the next sample; returns false when the loop ends.
-    __host__ __device__ bool next(int& seg, double& t_in, double& t_acc) {
-        while (acc < t_end) {
-            if (tis > Ti) {
-                tis = tis - Ti;
-                i++;
-                if (i >= M) return false;
-                Ti = T[i];
-                continue;
-            }
-            seg = i;
-            t_in = tis;
-            t_acc = acc;
-            return true;
-        }
-        return false;
-    }
-    __host__ __device__ void advance(double dt) {
-        tis = tis + dt;
-        acc = acc + dt;
-    }
-    // The next 8 samples at once when none of them rolls over into the next segment or
-    // reaches the end (the same additions, in the same order, as 8 next/advance steps;
-    // acc and tis only grow, so checking the 8th sample covers all).  False: nothing
-    // consumed, take single steps.
-    __device__ bool fast8(double dt, double (&tin)[8], double (&tac)[8]) {
-        double t = tis, a = acc;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            tin[k] = t;
-            tac[k] = a;
-            t = t + dt;
-            a = a + dt;
-        }
-        if (!(tac[7] < t_end) || tin[7] > Ti) return false;
-        tis = t;
-        acc = a;
-        return true;
-    }
-};
-
 // One wavefront per track: the lanes stage the segment times in LDS, lane 0 runs the
 // recurrence (every step reads T[i] from LDS, not from memory).
 __global__ __launch_bounds__(kWave) void k_sample_count(const double* __restrict__ seg_times,
@@ -637,15 +575,6 @@ __global__ __launch_bounds__(kWave) void k_sample_count(const double* __restrict
         }
         counts[t] = n;
     }
-}
-
-// Polynomial::evaluate(t, k) — polynomial.h:136-149
-// (Horner with fused multiply-adds: the sampled values are compared at 1e-6, the time
-// column, which does not go through here, exactly)
-__device__ __forceinline__ double poly_eval(const double* B, const double* c, double t, int k) {
-    double r = B[k * N + N - 1] * c[N - 1];
-    for (int j = N - 2; j >= k; --j) r = fma(r, t, B[k * N + j] * c[j]);
-    return r;
 }
 
 __global__ __launch_bounds__(kWave) void k_sample_rows(const double* __restrict__ seg_times,

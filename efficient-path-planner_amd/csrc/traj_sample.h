@@ -1,0 +1,110 @@
+// traj_sample.h — the sampling arithmetic of a fitted trajectory, shared by the row sampler
+// (minsnap.hip: k_sample_count, k_sample_rows, the host side of the refit) and the fused
+// first-collision check (trajcheck.hip): the evaluateRange time recurrence and the
+// polynomial evaluation.  One definition, so both produce the same sample times, segments
+// and positions bit for bit.  Plain C++ apart from the HIP qualifiers: a host program may
+// include it without the HIP runtime.
+#pragma once
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define EPP_TS_HD __host__ __device__
+#define EPP_TS_FN __host__ __device__ __forceinline__
+#else
+#include <cmath>
+#define EPP_TS_HD
+#define EPP_TS_FN inline
+#endif
+
+namespace epp {
+
+constexpr int kPolyCoeffs = 10;  // coefficients per polynomial (mav_trajectory_generation::Polynomial, N = 10)
+constexpr int kRowChunk = 512;   // samples per k_sample_rows round
+
+// Trajectory::evaluateRange control flow — src/trajectory.cpp:81-141.
+struct RangeIter {
+    const double* T;
+    int M, i;
+    double t_end, acc, tis, Ti;  // Ti = T[i], kept in a register (one LDS read per segment)
+    EPP_TS_HD void init(const double* T_, int M_) {
+        T = T_;
+        M = M_;
+        t_end = 0.0;  // max_time_ += segment.getTime()  trajectory.h:63-70
+        for (int k = 0; k < M; ++k) t_end = t_end + T[k];
+        acc = 0.0;
+        for (i = 0; i < M; ++i) {  // t_start = 0
+            acc = acc + T[i];
+            if (acc > 0.0) break;
+        }
+        if (i >= M) i = M - 1;
+        acc = acc - T[i];
+        tis = 0.0 - acc;
+        Ti = T[i];
+    }
+    // Advances to the next sample; returns false when the loop ends.
+    EPP_TS_HD bool next(int& seg, double& t_in, double& t_acc) {
+        while (acc < t_end) {
+            if (tis > Ti) {
+                tis = tis - Ti;
+                i++;
+                if (i >= M) return false;
+                Ti = T[i];
+                continue;
+            }
+            seg = i;
+            t_in = tis;
+            t_acc = acc;
+            return true;
+        }
+        return false;
+    }
+    EPP_TS_HD void advance(double dt) {
+        tis = tis + dt;
+        acc = acc + dt;
+    }
+    // The next 8 samples at once when none of them rolls over into the next segment or
+    // reaches the end (the same additions, in the same order, as 8 next/advance steps;
+    // acc and tis only grow, so checking the 8th sample covers all).  False: nothing
+    // consumed, take single steps.
+    EPP_TS_HD bool fast8(double dt, double (&tin)[8], double (&tac)[8]) {
+        double t = tis, a = acc;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+        for (int k = 0; k < 8; ++k) {
+            tin[k] = t;
+            tac[k] = a;
+            t = t + dt;
+            a = a + dt;
+        }
+        if (!(tac[7] < t_end) || tin[7] > Ti) return false;
+        tis = t;
+        acc = a;
+        return true;
+    }
+};
+
+// Polynomial::evaluate(t, k) — polynomial.h:136-149; B: the falling factorials
+// B[k][j] = j! / (j-k)! (src/polynomial.cpp:145-160), row-major 10 x 10
+// (Horner with fused multiply-adds: the sampled values are compared at 1e-6, the time
+// column, which does not go through here, exactly)
+EPP_TS_FN double poly_eval(const double* B, const double* c, double t, int k) {
+    constexpr int N = kPolyCoeffs;
+    double r = B[k * N + N - 1] * c[N - 1];
+    for (int j = N - 2; j >= k; --j) r = fma(r, t, B[k * N + j] * c[j]);
+    return r;
+}
+
+// poly_eval(B, c, t, 0) without the table: B[0][j] = 1 and 1 * c[j] is c[j] exactly, so the
+// same fused Horner steps give the same bits (tests/test_gpu_trajcheck.py compares them).
+EPP_TS_FN double poly_eval_pos(const double* c, double t) {
+    constexpr int N = kPolyCoeffs;
+    double r = c[N - 1];
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int j = N - 2; j >= 0; --j) r = fma(r, t, c[j]);
+    return r;
+}
+
+}  // namespace epp

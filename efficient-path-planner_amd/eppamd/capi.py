@@ -95,6 +95,7 @@ def lib() -> C.CDLL:
             "epp_sample_batch": (i32, [vp, vp, vp, i32, dp, vp, vp, vp, vp]),
             "epp_traj_peaks": (i32, [vp, vp, vp, i32, vp, vp, vp]),
             "epp_traj_scale_to_limits": (i32, [vp, vp, vp, i32, dp, dp, vp, vp, vp]),
+            "epp_traj_check_batch": (i32, [vp, vp, vp, vp, i32, dp, dp, vp, vp, vp]),
             "epp_generate_trajectory_limited_host": (i32, [vp, i32, dp, dp, dp, dp, vp, vp,
                                                            C.POINTER(C.POINTER(C.c_double)), C.POINTER(i64),
                                                            C.POINTER(C.c_double)]),
@@ -154,6 +155,7 @@ EXPORTED = [
     "epp_comm_allreduce_f64", "epp_comm_barrier", "epp_comm_available", "epp_knn_ws_box", "epp_knn_grid_ws_box",
     "epp_comm_set_timeout", "epp_comm_abort", "epp_check_and_generate_trajectory_host",
     "epp_traj_peaks", "epp_traj_scale_to_limits", "epp_generate_trajectory_limited_host",
+    "epp_traj_check_batch",
 ]
 
 
@@ -317,6 +319,18 @@ class World:
         self.check_motions_dev(d1.ptr, d2.ptr, n, can_pass_gate, mode, d_valid.ptr)
         sync()
         return d_valid.download(np.uint8, n)
+
+    def check_trajectories(self, Ts, Cs, dt: float, min_distance: float):
+        """epp_traj_check_batch on the lists minsnap_batch returns: per track the index of the
+        first sampled row (Trajectory::evaluateRange at dt) closer than min_distance to an OBB
+        and its time, (-1, -1.0) for a collision-free track.  Returns (int64[n], float64[n])."""
+        nt = len(Ts)
+        d_T, d_C, d_off, _, _ = _upload_tracks(Ts, Cs)
+        d_row, d_time = DeviceBuffer(8 * nt), DeviceBuffer(8 * nt)
+        check(lib().epp_traj_check_batch(self.handle, d_T.ptr, d_C.ptr, d_off.ptr, nt, float(dt), float(min_distance),
+                                         d_row.ptr, d_time.ptr, None))
+        sync()
+        return d_row.download(np.int64, nt), d_time.download(np.float64, nt)
 
 
 def minsnap_batch(tracks, v_max, a_max, v0=None, a0=None):

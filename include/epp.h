@@ -29,6 +29,9 @@
  *   epp_minsnap_batch / epp_sample_count / epp_sample_batch
  *       poly_traj::generateTrajectory (external/poly_traj/include/poly_traj/trajectory_generator.h:20,
  *       external/poly_traj/src/trajectory_generator.cpp:12-100), batched over tracks.
+ *   epp_traj_check_batch
+ *       PathPlanner::checkTrajectoryValidity (src/PathPlanner.cpp:267-280) of every fitted
+ *       track, from its coefficients: the first failing row per track.
  */
 #ifndef EPP_H_
 #define EPP_H_
@@ -215,6 +218,25 @@ epp_status epp_traj_peaks(const double* seg_times, const double* coeffs, const i
 epp_status epp_traj_scale_to_limits(double* seg_times, double* coeffs, const int32_t* wp_offsets,
                                     int32_t n_tracks, double v_max, double a_max, double* scale,
                                     int32_t* status, void* stream);
+/* PathPlanner::checkTrajectoryValidity (src/PathPlanner.cpp:267-280) for every track of a
+ * batch in the layout of epp_minsnap_batch, straight from the coefficients, in one launch
+ * and without writing a row: first_invalid[k] (n_tracks, device int64) is the index of the
+ * first row of Trajectory::evaluateRange(0, max_time, dt) (src/trajectory.cpp:81-141)
+ * whose position fails World::checkPointValidity(p, min_distance) (src/World.cpp:106-128),
+ * -1 if every row passes (a track without rows, e.g. of one waypoint or with the NaN times
+ * of a failed fit, passes, as the reference's loop returns true).  first_time[k] (n_tracks,
+ * device f64, may be NULL) is that row's time column as epp_sample_batch writes it with
+ * t0 == NULL, -1.0 for a valid track.  The answers are those of epp_sample_count +
+ * epp_sample_batch + epp_check_states_mindist on the rows' columns 0 / 3 / 6, bit for bit
+ * (the same recurrence, Horner steps and predicates).  Stream-ordered, no host
+ * synchronisation and no allocation; a stale world index is rebuilt first, as by
+ * epp_check_states_mindist, so the call can be captured (epp_graph_begin) after
+ * epp_world_build_index.  EPP_ERR_INVALID_ARGUMENT (before any device work) for a NULL
+ * world, n_tracks < 0, dt <= 0 or not finite, or a NULL seg_times, coeffs, wp_offsets or
+ * first_invalid with n_tracks > 0; n_tracks == 0 launches nothing. */
+epp_status epp_traj_check_batch(const epp_world* w, const double* seg_times, const double* coeffs,
+                                const int32_t* wp_offsets, int32_t n_tracks, double dt, double min_distance,
+                                int64_t* first_invalid, double* first_time, void* stream);
 
 /* ---- batch planner building blocks (device pointers) ------------------------------- */
 /* Replace OMPL's sampler / nearest-neighbour structure behind PathPlanner::planPath

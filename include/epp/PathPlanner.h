@@ -106,6 +106,19 @@ public:
                                             const std::vector<Vec3>& waypoints, double vMax, double aMax,
                                             double samplingInterval, double startTimeOffset, const Vec3& v0,
                                             const Vec3& a0, Matrix& result) const;
+    // Which of K candidate waypoint sets give a collision-free trajectory, and where the
+    // others first collide (an addition of this build): poly_traj::generateTrajectory's fit of
+    // every set (epp_minsnap_batch) and checkTrajectoryValidity of each fit's rows at
+    // samplingInterval (epp_traj_check_batch: no row is written) on one stream against the
+    // planner's world; the call itself synchronises once, at the end (epp_minsnap_batch reads
+    // the track offsets back to size its launch: a second, short host wait inside it).  firstInvalidRow[k]: the index of set
+    // k's first row closer than minDistance to an obstacle, -1 if none; firstInvalidTime
+    // (optional): that row's time, -1.0 if none.  Returns true iff every set is valid.
+    // Throws std::invalid_argument("At least two waypoints are required") for a set with
+    // fewer, std::runtime_error for a failed fit, as generateTrajectory.
+    bool checkCandidateTrajectories(const std::vector<std::vector<Vec3>>& waypointSets, double v_max, double a_max,
+                                    double dt, double minDistance, std::vector<long>& firstInvalidRow,
+                                    std::vector<double>* firstInvalidTime = nullptr) const;
     std::vector<Vec3> includeGates2(std::vector<std::vector<Vec3>> waypoints) const;
     // planPaths of consecutive gate-to-gate segments, then includeGates2 of their paths (an
     // addition of this build, for OnlineTrajGenerator::preComputeTraj): the same answers as

@@ -1,0 +1,145 @@
+#!/usr/bin/env python3
+"""Device time of the fused first-collision check (epp_traj_check_batch) beside the
+composition it replaces, on 4096 fitted tracks of 12 segments (seeds 10_000 + k, v_max = 1.0,
+a_max = 2.0) sampled at dt = 0.01 against the 72-OBB world (synth.track_world(42),
+configs/config_filling.json), min_distance 0.05:
+
+    fused      epp_traj_check_batch: one launch, no row written
+    composed   epp_sample_count + epp_sample_batch (80 B per row to HBM) +
+               epp_check_states_mindist on the contiguous n x 3 repack of columns 0 / 3 / 6
+               (the repack itself, a host step today, is made once outside the timing)
+
+in two cases: "valid" (every track lifted 10 m, above every obstacle: no early exit, every row
+evaluated and checked) and "mixed" (the tracks as fitted: valid and colliding ones).
+
+hipEvent pairs on one stream around each call, --warmup untimed launches, then --reps timed
+ones; median, min and max of each, the three composed calls timed one by one and summed (each
+of the two sampling calls reads the track offsets back inside its pair, as it always does).
+
+    python scripts/traj_check_time.py [--reps 20] [--out profiles/traj_check_time.json]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "efficient-path-planner_amd"))
+
+from eppamd import capi, config, synth  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--tracks", type=int, default=4096)
+    ap.add_argument("--dt", type=float, default=0.01)
+    ap.add_argument("--min-distance", type=float, default=0.05)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    L = capi.lib()
+    nt, dt, md = a.tracks, a.dt, a.min_distance
+    cfg = config.load(os.path.join(ROOT, "configs", "config_filling.json"))
+    rg, ro = config.inflate_radii(cfg)
+    world = capi.World(capi.build_obbs(config.geometry(cfg), *synth.track_world(42)), rg, ro)
+    world.build_index()
+    stream = C.c_void_p()
+    capi.check(L.epp_stream_create(C.byref(stream)))
+    ev = [C.c_void_p(), C.c_void_p()]
+    for e in ev:
+        capi.check(L.epp_event_create(C.byref(e)))
+    off = np.arange(nt + 1, dtype=np.int32) * 13
+    d_off = capi.DeviceBuffer.from_array(off, stream)
+    d_T, d_C = capi.DeviceBuffer(8 * 12 * nt), capi.DeviceBuffer(240 * 12 * nt)
+    d_st, d_cnt, d_roff = capi.DeviceBuffer(4 * nt), capi.DeviceBuffer(8 * nt), capi.DeviceBuffer(8 * nt)
+    d_first, d_time = capi.DeviceBuffer(8 * nt), capi.DeviceBuffer(8 * nt)
+
+    def timed(fn):
+        ms = []
+        for r in range(a.warmup + a.reps):
+            capi.check(L.epp_event_record(ev[0], stream))
+            fn()
+            capi.check(L.epp_event_record(ev[1], stream))
+            capi.check(L.epp_stream_sync(stream))
+            x = C.c_float(0)
+            capi.check(L.epp_event_elapsed_ms(ev[0], ev[1], C.byref(x)))
+            if r >= a.warmup:
+                ms.append(x.value)
+        ms = np.array(ms)
+        return {"median_ms": float(np.median(ms)), "min_ms": float(ms.min()), "max_ms": float(ms.max())}
+
+    res = {"tracks": nt, "segments": 12, "dt": dt, "min_distance": md, "obbs": world.n, "reps": a.reps,
+           "warmup": a.warmup}
+    for case, lift in (("valid", 10.0), ("mixed", 0.0)):
+        tracks = [synth.random_track_waypoints(10_000 + k, 12) + [0.0, 0.0, lift] for k in range(nt)]
+        d_wp = capi.DeviceBuffer.from_array(np.ascontiguousarray(np.concatenate(tracks)), stream)
+        capi.check(L.epp_minsnap_batch(d_wp.ptr, d_off.ptr, nt, 1.0, 2.0, None, None, d_T.ptr, d_C.ptr, d_st.ptr,
+                                       stream))
+        capi.check(L.epp_stream_sync(stream))
+        assert (d_st.download(np.int32, nt, stream) == 0).all()
+
+        def count():
+            capi.check(L.epp_sample_count(d_T.ptr, d_off.ptr, nt, dt, d_cnt.ptr, stream))
+
+        count()
+        capi.check(L.epp_stream_sync(stream))
+        cnt = d_cnt.download(np.int64, nt, stream)
+        roff = np.zeros(nt + 1, np.int64)
+        roff[1:] = np.cumsum(cnt)
+        n_rows = int(roff[-1])
+        d_roff.upload(roff[:-1].copy(), stream)
+        d_rows, d_xyz, d_valid = capi.DeviceBuffer(80 * n_rows), capi.DeviceBuffer(24 * n_rows), capi.DeviceBuffer(n_rows)
+
+        def rows():
+            capi.check(L.epp_sample_batch(d_T.ptr, d_C.ptr, d_off.ptr, nt, dt, None, d_roff.ptr, d_rows.ptr, stream))
+
+        def states():
+            capi.check(L.epp_check_states_mindist(world.handle, d_xyz.ptr, n_rows, md, d_valid.ptr, stream))
+
+        def fused():
+            capi.check(L.epp_traj_check_batch(world.handle, d_T.ptr, d_C.ptr, d_off.ptr, nt, dt, md, d_first.ptr,
+                                              d_time.ptr, stream))
+
+        rows()
+        capi.check(L.epp_stream_sync(stream))
+        host_rows = d_rows.download(np.float64, n_rows * 10, stream).reshape(-1, 10)
+        d_xyz.upload(np.ascontiguousarray(host_rows[:, [0, 3, 6]]), stream)  # the repack (untimed)
+        r = {"rows": n_rows}
+        r["fused"] = timed(fused)
+        r["sample_count"] = timed(count)
+        r["sample_batch"] = timed(rows)
+        r["check_states_mindist"] = timed(states)
+        parts = ("sample_count", "sample_batch", "check_states_mindist")
+        r["composed"] = {k: float(sum(r[p][k] for p in parts)) for k in ("median_ms", "min_ms", "max_ms")}
+        r["composed_over_fused"] = r["composed"]["median_ms"] / r["fused"]["median_ms"]
+        # the same answers, or the times compare different work
+        first = d_first.download(np.int64, nt, stream)
+        flags = d_valid.download(np.uint8, n_rows, stream)
+        exp = np.full(nt, -1, np.int64)
+        bad = np.flatnonzero(flags == 0)
+        tr = np.searchsorted(roff, bad, side="right") - 1
+        uniq, idx = np.unique(tr, return_index=True)
+        exp[uniq] = bad[idx] - roff[uniq]
+        assert np.array_equal(first, exp), "fused and composed answers differ"
+        r["tracks_valid"] = int((first < 0).sum())
+        r["rows_before_first_collision"] = int(np.where(first < 0, cnt, first + 1).sum())
+        res[case] = r
+        for b in (d_rows, d_xyz, d_valid, d_wp):
+            b.free()
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    for e in ev:
+        L.epp_event_destroy(e)
+    capi.check(L.epp_stream_destroy(stream))
+
+
+if __name__ == "__main__":
+    main()
