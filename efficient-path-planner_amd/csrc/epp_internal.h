@@ -11,8 +11,10 @@
 //                                coarse cell (x, y, z) the OBB's AABB touches
 //   double  soa[EPP_NF][n_pad]   field-major OBB table (see enum below)
 //   double  aos[n_obb][17]       the OBB table again as 136-byte records (exact path)
+//   double  pt[n_obb][16]        128-byte point records of the plain point test (thresholds
+//                                inflated on the host, chunks swizzled: kPtDoubles below)
 //   uint32  hdr[n_lists]         candidate lists of the fine cells: start << 12 | count
-//   uint16  ids[...]             the lists' OBB ids
+//   uint16  ids[...]             the lists' OBB ids, bit 15 = the OBB is filling
 //   uint8   cls8[ncells+1]       the fine-cell classes as bytes, when n_lists <= 256 (what
 //                                k_states_v5 stages; else it stages the u16 cls[])
 //   -------------------------    (everything above: staged into LDS by k_states_bm)
@@ -181,6 +183,28 @@ enum Field : int {
 constexpr int kRecDoubles = 17;
 constexpr int R_META = 16;
 
+// Point record of the plain (non-MINDIST) point test of k_states_v5 / k_states_v4: 16 doubles
+// (128 B, 16-byte aligned: seven ds_read_b128).  Fields F_LOX .. F_SIN in the order of enum
+// Field, then the test's thresholds tx ty tz where the half sizes are,
+//   t = filling ? h : h + (is_gate ? r_gate : r_obst)
+// (the additions and selects rec_hit does per pair, done once per index build), two spare
+// doubles.  The record's eight 16-byte chunks are stored XOR-swizzled: chunk c of record i
+// is chunk c ^ ((i >> 1) & 7) of its 128 bytes, so that lanes reading chunk c of records
+// with different i mod 16 use different 16-byte slots of the 256-byte LDS bank row
+// (ds_read_b128 banks are (a / 4) mod 64: unswizzled, chunk c of every second record would
+// share four banks: measured 7.26-7.33 us per C2 launch against 6.88-7.10 us swizzled,
+// profiles/r09_states_rec_ab.txt).
+constexpr int kPtDoubles = 16;
+constexpr int P_TX = F_HX, P_TY = F_HY, P_TZ = F_HZ;
+// byte offset of 16-byte chunk c (0..7) of point record i, from the first record
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+constexpr uint32_t pt_chunk_off(uint32_t i, uint32_t c) { return (i << 7) + ((c ^ ((i >> 1) & 7u)) << 4); }
+// Candidate-list ids carry the OBB's filling flag in bit 15 (worlds of at most 32,768 OBBs;
+// WorldView::id_mask says whether): the point test learns it from the id it reads anyway.
+constexpr uint32_t kIdFill = 0x8000u;
+
 constexpr size_t kListMaxLen = 4095;  // OBBs per fine-cell list (12-bit count)
 // LDS bytes k_states_v5 stages per workgroup (records, lists, class table): the class
 // grid is coarsened until the world fits; the copy is register-staged, so this also
@@ -213,9 +237,11 @@ struct WorldView {
     float fmaxx, fmaxy, fmaxz; // 4 * n - 1: largest fine index
     double r_gate, r_obst;    // inflate radii (src/World.cpp:89-90)
     // fine cell classes (k_states fast path)
-    uint32_t off_aos;         // OBB records (kRecDoubles each), then the lists
+    uint32_t off_aos;         // OBB records (kRecDoubles each), then the point records
+    uint32_t off_pt;          // point records (kPtDoubles each), then the lists
     uint32_t off_lists;       // list headers (u32: start << 12 | count)
-    uint32_t off_ids;         // list OBB ids (u16)
+    uint32_t off_ids;         // list OBB ids (u16; bit 15: filling, see id_mask)
+    uint32_t id_mask;         // 0x7FFF: ids carry kIdFill (n_obb <= 32768), else 0xFFFF
     uint32_t n_lists;
     uint32_t off_bitmap;      // cls[] (u16 per fine cell)
     uint32_t bm_words;        // index of the zero sentinel class

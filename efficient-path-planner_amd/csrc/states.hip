@@ -237,12 +237,17 @@ __global__ __launch_bounds__(kBlock4) void k_states_v4(const WorldView* __restri
         }
     };
     if (items > 0) load(it);
-    // records + lists: [off_aos, off_bitmap) of the blob, staged into LDS
-    const uint32_t lists_off = wv->off_lists - wv->off_aos, ids_off = wv->off_ids - wv->off_aos;
+    // records + lists: [off_aos, off_pt) and [off_lists, off_bitmap) of the blob, staged into
+    // LDS back to back (the point records between them stay behind)
+    const uint32_t rec_bytes = wv->off_pt - wv->off_aos;
+    const uint32_t lists_off = STAGE ? rec_bytes : wv->off_lists - wv->off_aos;
+    const uint32_t ids_off = lists_off + (wv->off_ids - wv->off_lists);
+    const uint32_t id_mask = wv->id_mask;
     const double rg = wv->r_gate, ro = wv->r_obst;
     const unsigned char* xbase;
     if (STAGE) {
-        stage_copy(lds_blob, wv->blob + wv->off_aos, stage_bytes, kBlock4);
+        stage_copy(lds_blob, wv->blob + wv->off_aos, rec_bytes, kBlock4);
+        stage_copy(lds_blob + rec_bytes, wv->blob + wv->off_lists, stage_bytes - rec_bytes, kBlock4);
         xbase = lds_blob;  // (the first barrier below orders the copy before any use)
     } else {
         xbase = wv->blob + wv->off_aos;
@@ -280,7 +285,7 @@ __global__ __launch_bounds__(kBlock4) void k_states_v4(const WorldView* __restri
             }
             __syncthreads();
             for (uint32_t e = threadIdx.x; e < T; e += kBlock4)  // only the first ceil(T/64) waves
-                q.hit[e] = states_exact_rec<MINDIST>(xbase, lists_off, ids_off, rg, ro, q.x[e], q.y[e], q.z[e], q.cls[e],
+                q.hit[e] = states_exact_rec<MINDIST>(xbase, lists_off, ids_off, id_mask, rg, ro, q.x[e], q.y[e], q.z[e], q.cls[e],
                                                      can_pass, md)
                                ? 1
                                : 0;
@@ -306,7 +311,7 @@ __global__ __launch_bounds__(kBlock4) void k_states_v4(const WorldView* __restri
         const int64_t i = n - 1;
         const double px = xyz[3 * i], py = xyz[3 * i + 1], pz = xyz[3 * i + 2];
         const uint32_t c = bp.cls[cls_index(bp, px, py, pz)];
-        const bool ok = !(c != 0u && states_exact_rec<MINDIST>(xbase, lists_off, ids_off, rg, ro, px, py, pz, c, can_pass, md));
+        const bool ok = !(c != 0u && states_exact_rec<MINDIST>(xbase, lists_off, ids_off, id_mask, rg, ro, px, py, pz, c, can_pass, md));
         valid[i] = ok ? 1 : 0;
         if (COMPACT && ok) compact_idx[atomicAdd(n_valid, 1ull)] = (int32_t)i;
     }
@@ -381,7 +386,7 @@ __device__ unsigned long long g_states_tl[kTlWaves][kTlWords];
 // The world's parameters reach the kernel by value (V5Args, filled on the host by
 // v5_args): nothing on a wave's way to its first load or to the staging barrier is
 // fetched through a pointer into device memory.  The arguments the first loads need
-// (stage_src = blob + off_aos, xyz, groups, stage_bytes) lead the list, scalars and
+// (stage_src = blob + off_pt, or + off_aos for MINDIST; xyz, groups, stage_bytes) lead the list, scalars and
 // pointers only, so that the kernel-argument preload (Makefile, states.o) delivers
 // them in SGPRs at wave launch; the struct comes last (a leading struct disables the
 // preload).
@@ -390,7 +395,8 @@ struct V5Args {
     uint32_t cls_off, cls_nz_off;  // the class table (bytes or u16) / the sparse classes' bytes
     uint32_t nx, ny, nz;          // class cells per axis
     float ox, oy, oz, ix, iy, iz;  // cell coordinate f = fmaf((float)p, i, o)
-    double rg, ro;                // inflate radii
+    // (no inflate radii: the plain test's thresholds come inflated in the point records, the
+    // MINDIST one inflates by its own argument)
 };
 
 // PREFETCH: groups per lane > 1 (the next group's loads overlap this one's work);
@@ -433,7 +439,8 @@ void k_states_v5(const unsigned char* stage_src, const double* xyz,
             dst[2 * k + 1] = t.y;
         }
     };
-    // [off_aos, blob_bytes): records, list headers, list ids, class table.  The copy's
+    // [off_pt, ...): point records, list headers, list ids, class table (MINDIST: from off_aos,
+    // the 17-double records first, the point records riding along unused).  The copy's
     // loads are issued BEFORE the group's loads and stored after them, so the stores
     // wait on a counted vmcnt that leaves the group's HBM loads in flight, and the
     // barrier below never waits on HBM.  Every lane loads and stores every chunk slot
@@ -469,12 +476,20 @@ void k_states_v5(const unsigned char* stage_src, const double* xyz,
     [[maybe_unused]] const unsigned char* cls_nz = lds_blob + wa.cls_nz_off;  // (sparse classes)
     const uint32_t* hdrs = reinterpret_cast<const uint32_t*>(lds_blob + lists_off);
     const uint16_t* ids_all = reinterpret_cast<const uint16_t*>(lds_blob + ids_off);
-    const double* recs = reinterpret_cast<const double*>(lds_blob);
     const float ox = wa.ox, oy = wa.oy, oz = wa.oz, ix = wa.ix, iy = wa.iy, iz = wa.iz;
     const uint32_t nx = wa.nx, ny = wa.ny, nz = wa.nz;
-    const double rg = wa.rg, ro = wa.ro;
     __syncthreads();
     EPP_STL(1);
+    // One (state, candidate) test; `ide`: the list's id entry (bit 15 = filling).  The staged
+    // copy starts with the records the instantiation tests on: the point records (plain) or
+    // the 17-double records (MINDIST: its radius is md, the world's radii are not used).
+    auto hit_of = [&](uint32_t ide, double px, double py, double pz) -> bool {
+        if constexpr (MINDIST)
+            return rec_hit<true>(reinterpret_cast<const double*>(lds_blob) + (size_t)(ide & (kIdFill - 1u)) * kRecDoubles,
+                                 0.0, 0.0, px, py, pz, false, md);
+        else
+            return point_rec_hit(lds_blob, ide, px, py, pz, can_pass != 0);
+    };
     auto cell_of = [&](double px, double py, double pz) -> uint32_t {
         const uint32_t cx = cell_axis5(px, ox, ix, nx - 1), cy = cell_axis5(py, oy, iy, ny - 1),
                        cz = cell_axis5(pz, oz, iz, nz - 1);
@@ -608,9 +623,7 @@ void k_states_v5(const unsigned char* stage_src, const double* xyz,
                     const uint32_t h0 = dpp_incl_max(lane_scatter(own0 ? poff : 0u, own0 ? head : head0));
                     auto test = [&](uint32_t h, uint32_t q) {
                         const uint32_t e = (h >> 21) - 1u;  // (h != 0: position 0 is a head)
-                        return q < ptot &&
-                               rec_hit<MINDIST>(recs + (size_t)ids_all[(h & 0x1FFFFFu) + q - 128u] * kRecDoubles, rg, ro,
-                                                qu->x[e], qu->y[e], qu->z[e], can_pass != 0, md);
+                        return q < ptot && hit_of(ids_all[(h & 0x1FFFFFu) + q - 128u], qu->x[e], qu->y[e], qu->z[e]);
                     };
                     unsigned long long m1 = 0ull;
                     uint32_t h1 = 0u;
@@ -635,12 +648,9 @@ void k_states_v5(const unsigned char* stage_src, const double* xyz,
                     const bool hi = end > 64u && bits(m1, poff > 64u ? poff - 64u : 0u, end - max(poff, 64u));
                     hit_e = act && (lo || hi);
                 } else if (act) {  // long lists: each queued state walks its own
-                    const double* rc = reinterpret_cast<const double*>(lds_blob);
                     const uint16_t* idl = reinterpret_cast<const uint16_t*>(lds_blob + ids_off) + first;
                     const double px = qu->x[lane], py = qu->y[lane], pz = qu->z[lane];
-                    for (uint32_t j = 0; j < cnt; ++j)
-                        hit_e |= rec_hit<MINDIST>(rc + (size_t)idl[j] * kRecDoubles, rg, ro, px, py, pz, can_pass != 0,
-                                                  md);
+                    for (uint32_t j = 0; j < cnt; ++j) hit_e |= hit_of(idl[j], px, py, pz);
                 }
                 // back to the owners: state slot r0 + e lives on lane e
                 const unsigned long long hm = __builtin_amdgcn_ballot_w64(hit_e);
@@ -711,8 +721,14 @@ void k_states_v5(const unsigned char* stage_src, const double* xyz,
         const uint32_t cell[1] = {cell_of(px, py, pz)};
         uint32_t c[1], occ[1];
         classes_of(cell, c, occ);
-        const bool ok = !(occ[0] != 0u && states_exact_rec<MINDIST>(lds_blob, lists_off, ids_off, rg, ro, px, py, pz, c[0],
-                                                              can_pass, md));
+        bool hit = false;
+        if (occ[0] != 0u) {
+            if constexpr (MINDIST)
+                hit = states_exact_rec<true>(lds_blob, lists_off, ids_off, kIdFill - 1u, 0.0, 0.0, px, py, pz, c[0], 0, md);
+            else
+                hit = states_exact_pt(lds_blob, lists_off, ids_off, px, py, pz, c[0], can_pass);
+        }
+        const bool ok = !hit;
         valid[i] = ok ? 1 : 0;
         if (COMPACT && ok) compact_idx[atomicAdd(n_valid, 1ull)] = (int32_t)i;
     }
@@ -734,29 +750,33 @@ StatesKernel forced_kernel() {
 }
 
 // k_states_v5 stages records, lists and the class table (bytes when there are, else u16):
-// [off_aos, end of the byte table) or [off_aos, blob_bytes)
-uint32_t v5_staged(const WorldView& w) {
-    return (w.off_cls8 ? ((w.off_cls8 + w.cls8_bytes + 15u) & ~15u) : w.blob_bytes) - w.off_aos;
+// [start, end of the byte table) or [start, blob_bytes), from the point records on (plain) or
+// from the 17-double records on (MINDIST: the point records in between are copied with them)
+uint32_t v5_start(const WorldView& w, bool mindist) { return mindist ? w.off_aos : w.off_pt; }
+uint32_t v5_staged(const WorldView& w, bool mindist) {
+    return (w.off_cls8 ? ((w.off_cls8 + w.cls8_bytes + 15u) & ~15u) : w.blob_bytes) - v5_start(w, mindist);
 }
 // The by-value world parameters of k_states_v5 (offsets relative to the staged copy)
-V5Args v5_args(const WorldView& w) {
+V5Args v5_args(const WorldView& w, bool mindist) {
     V5Args a{};
-    a.lists_off = w.off_lists - w.off_aos;
-    a.ids_off = w.off_ids - w.off_aos;
-    a.cls_off = (w.off_cls8 ? w.off_cls8 : w.off_bitmap) - w.off_aos;
+    const uint32_t start = v5_start(w, mindist);
+    a.lists_off = w.off_lists - start;
+    a.ids_off = w.off_ids - start;
+    a.cls_off = (w.off_cls8 ? w.off_cls8 : w.off_bitmap) - start;
     a.cls_nz_off = a.cls_off + ((w.bm_words + 1u + 31u) >> 5) * 8u;
     a.nx = (uint32_t)w.bnx; a.ny = (uint32_t)w.bny; a.nz = (uint32_t)w.bnz;
     a.ox = w.bofx; a.oy = w.bofy; a.oz = w.bofz;
     a.ix = w.bix; a.iy = w.biy; a.iz = w.biz;
-    a.rg = w.r_gate; a.ro = w.r_obst;
     return a;
 }
 // Launches without a full group (n < 4) aim their (ignored) state loads at the staging
 // source: it must hold the 96 bytes a lane loads.
 constexpr uint32_t kV5DummyBytes = 96;
-bool v5_fits(const WorldView& w) {
-    const uint32_t sb = v5_staged(w);
-    return sb <= kStageBudget && sb + 16u + queue5_bytes<1024>() <= 160u * 1024u;
+// (the list ids carry the filling flag the point test needs: id_mask; always so for a world
+// that fits, <= 512 OBBs)
+bool v5_fits(const WorldView& w, bool mindist) {
+    const uint32_t sb = v5_staged(w, mindist);
+    return sb <= kStageBudget && sb + 16u + queue5_bytes<1024>() <= 160u * 1024u && w.id_mask == kIdFill - 1u;
 }
 
 // Launch shape of k_states_v5.  Single pass (every lane one group, e.g. 1M states on 256
@@ -795,12 +815,14 @@ V5Shape v5_shape(int64_t n, uint32_t sb) {
     return r;
 }
 
-bool v4_stage(const WorldView& w) { return (w.off_bitmap - w.off_aos) + sizeof(StateQueue4) <= 160u * 1024u; }
+// k_states_v4 stages the records and the lists (not the point records between them)
+uint32_t v4_staged(const WorldView& w) { return (w.off_pt - w.off_aos) + (w.off_bitmap - w.off_lists); }
+bool v4_stage(const WorldView& w) { return v4_staged(w) + sizeof(StateQueue4) <= 160u * 1024u; }
 // resident workgroups only (every block loops): LDS-limited, at most 3 per CU
 int v4_grid(const WorldView& w, int64_t n) {
     const int64_t items = std::max<int64_t>(1, n / 2);
     const int64_t need = (items + kBlock4 - 1) / kBlock4;
-    const uint32_t lds = sizeof(StateQueue4) + (v4_stage(w) ? w.off_bitmap - w.off_aos : 0u);
+    const uint32_t lds = sizeof(StateQueue4) + (v4_stage(w) ? v4_staged(w) : 0u);
     const int per_cu = std::max(1, std::min<int>(3, (int)((160u * 1024u) / lds)));
     const int64_t cap = (int64_t)cu_count() * per_cu;
     return (int)std::max<int64_t>(1, std::min(need, cap));
@@ -814,17 +836,17 @@ epp_status launch_states(const WorldView& w, const WorldView* dw, const double* 
     const char* what = MINDIST ? "epp_check_states_mindist" : "epp_check_states";
     const StatesKernel want = forced_kernel();
     const bool x16 = (reinterpret_cast<uintptr_t>(xyz) & 15) == 0;
-    if (want == StatesKernel::V5 && v5_fits(w) && x16 && (reinterpret_cast<uintptr_t>(valid) & 3) == 0 &&
-        (n >= 4 || w.blob_bytes - w.off_aos >= kV5DummyBytes)) {
-        const uint32_t sb = v5_staged(w);
+    if (want == StatesKernel::V5 && v5_fits(w, MINDIST) && x16 && (reinterpret_cast<uintptr_t>(valid) & 3) == 0 &&
+        (n >= 4 || w.blob_bytes - v5_start(w, MINDIST) >= kV5DummyBytes)) {
+        const uint32_t sb = v5_staged(w, MINDIST);
         V5Shape sh = v5_shape(n, sb);
         if (sh.bs == 256 && compact_idx) {  // (the 256-thread shape is instantiated without compaction)
             sh.bs = 512;
             sh.grid = (int)std::max<int64_t>(1, (sh.gN + 511) / 512);
         }
         const uint32_t dyn = sb + 16u;  // the staged world + the dummy slot of the copy
-        const unsigned char* src = w.blob + w.off_aos;
-        const V5Args wa = v5_args(w);
+        const unsigned char* src = w.blob + v5_start(w, MINDIST);
+        const V5Args wa = v5_args(w, MINDIST);
 #define EPP_LAUNCH_V5S(C, B, P, C8, SC)                                                                              \
     do {                                                                                                             \
         allow_lds(k_states_v5<MINDIST, C, B, P, 4, C8, SC>, queue5_bytes<B>());                                      \
@@ -868,7 +890,7 @@ epp_status launch_states(const WorldView& w, const WorldView* dw, const double* 
     }
     if (want != StatesKernel::Generic && x16 && (reinterpret_cast<uintptr_t>(valid) & 1) == 0 &&
         n / 2 < 0xFFFFFFFFll) {
-        const uint32_t sb = w.off_bitmap - w.off_aos;
+        const uint32_t sb = v4_staged(w);
         const bool stg = v4_stage(w);
         const int g4 = v4_grid(w, n);
         const uint32_t items = (uint32_t)(n / 2);

@@ -339,7 +339,10 @@ bool build_blob(HostWorld& hw, const epp_obb* obbs, int n) {
             continue;
         }
         // k_states_v5 stages records + lists + class table into LDS: keep that part
-        // within kStageBudget by coarsening the class grid (down to 4096 cells)
+        // within kStageBudget by coarsening the class grid (down to 4096 cells).  (Sized by
+        // the 136-byte records: the plain instantiations stage the 128-byte point records
+        // instead and always fit; the MINDIST ones stage both images and go to k_states_v4
+        // when that exceeds the budget.)
         const size_t staged = align16((size_t)n * kRecDoubles * 8) + align16(hdr.size() * 4 + flat.size() * 2) +
                               align16(cls.size() * 2);
         if (staged > kStageBudget && target > 4096.0) {
@@ -371,8 +374,28 @@ bool build_blob(HostWorld& hw, const epp_obb* obbs, int n) {
         uint64_t m = meta[i];
         std::memcpy(&r[R_META], &m, 8);
     }
+    // Point records of the plain point test (kPtDoubles doubles each, layout in
+    // epp_internal.h): the thresholds are the additions and selects of rec_hit, in double
+    const bool id_flags = n <= 32768;  // bit 15 of a list id is free
+    std::vector<double> pts((size_t)n * kPtDoubles, 0.0);
+    for (int i = 0; i < n; ++i) {
+        const double* a = &aos[(size_t)i * kRecDoubles];
+        const bool fill = (meta[i] & META_FILLING) != 0u;
+        const double r = (meta[i] & META_GATE) ? hw.r_gate : hw.r_obst;
+        double f[kPtDoubles] = {};
+        for (int k = 0; k <= F_SIN; ++k) f[k] = a[k];
+        const double ix = a[F_HX] + r, iy = a[F_HY] + r, iz = a[F_HZ] + r;
+        f[P_TX] = fill ? a[F_HX] : ix;
+        f[P_TY] = fill ? a[F_HY] : iy;
+        f[P_TZ] = fill ? a[F_HZ] : iz;
+        char* dst = reinterpret_cast<char*>(pts.data());
+        for (uint32_t c = 0; c < 8; ++c) std::memcpy(dst + pt_chunk_off((uint32_t)i, c), &f[2 * c], 16);
+    }
+    if (id_flags)
+        for (auto& id : flat) id = (uint16_t)(id | ((meta[id] & META_FILLING) ? kIdFill : 0u));
     const size_t off_aos = align16(off_soa + soa.size() * sizeof(double));
-    const size_t off_lists = align16(off_aos + aos.size() * sizeof(double));
+    const size_t off_pt = align16(off_aos + aos.size() * sizeof(double));
+    const size_t off_lists = off_pt + pts.size() * sizeof(double);
     const size_t off_ids = off_lists + hdr.size() * 4;
     // byte classes (k_states_v5 stages them instead of the u16 table) when the lists fit.
     // Sparse form: per 32 cells one u64
@@ -515,10 +538,13 @@ bool build_blob(HostWorld& hw, const epp_obb* obbs, int n) {
     std::memcpy(b + off_meta, meta.data(), meta.size() * 4);
     std::memcpy(b + off_soa, soa.data(), soa.size() * sizeof(double));
     if (!aos.empty()) std::memcpy(b + off_aos, aos.data(), aos.size() * sizeof(double));
+    if (!pts.empty()) std::memcpy(b + off_pt, pts.data(), pts.size() * sizeof(double));
     std::memcpy(b + off_lists, hdr.data(), hdr.size() * 4);
     if (!flat.empty()) std::memcpy(b + off_ids, flat.data(), flat.size() * 2);
     v.off_ids = (uint32_t)off_ids;
+    v.id_mask = id_flags ? kIdFill - 1u : 0xFFFFu;
     v.off_aos = (uint32_t)off_aos;
+    v.off_pt = (uint32_t)off_pt;
     std::memcpy(b + off_bm, cls.data(), cls.size() * 2);
     if (!slab.empty()) std::memcpy(b + off_slab, slab.data(), slab.size() * 4);
     v.off_slab = (uint32_t)off_slab;
@@ -880,7 +906,8 @@ extern "C" epp_status epp_dbg_build_blob(const epp_obb* obbs, int32_t n, double 
 
 // Debug entry (not part of include/epp.h): the class-grid layout of a world's index, host
 // build only.  out: off_aos, off_lists, off_ids, off_cls8, off_bitmap, blob_bytes, n_lists,
-// class cells (bm_words), bnx, bny, bnz, staged bytes of k_states_v5.
+// class cells (bm_words), bnx, bny, bnz, staged bytes of k_states_v5 (the plain
+// instantiations: from the point records on).
 extern "C" epp_status epp_dbg_class_layout(const epp_obb* obbs, int32_t n, double r_gate, double r_obst,
                                            int64_t out[12]) {
     if (!out || n < 0 || (n > 0 && !obbs)) return EPP_ERR_INVALID_ARGUMENT;
@@ -892,8 +919,40 @@ extern "C" epp_status epp_dbg_class_layout(const epp_obb* obbs, int32_t n, doubl
     const int64_t vals[12] = {v.off_aos, v.off_lists, v.off_ids, v.off_cls8, v.off_bitmap, v.blob_bytes, v.n_lists,
                               v.bm_words, v.bnx, v.bny, v.bnz,
                               (int64_t)((v.off_cls8 ? ((v.off_cls8 + v.cls8_bytes + 15u) & ~15u) : v.blob_bytes) -
-                                        v.off_aos)};
+                                        v.off_pt)};
     for (int k = 0; k < 12; ++k) out[k] = vals[k];
+    return EPP_OK;
+}
+
+// Debug entry (not part of include/epp.h): the point-record image of a world's index, host
+// build only.  recs17: the n AoS records (kRecDoubles doubles each), pt16: the n point
+// records with their chunks in field order (unswizzled), ids: the first ids_cap list ids as
+// stored (bit 15 = filling).  out: off_aos, off_pt, off_lists, off_ids, number of list ids,
+// id_mask.
+extern "C" epp_status epp_dbg_point_records(const epp_obb* obbs, int32_t n, double r_gate, double r_obst,
+                                            double* recs17, double* pt16, uint16_t* ids, int64_t ids_cap,
+                                            int64_t out[6]) {
+    if (!out || n < 0 || (n > 0 && (!obbs || !recs17 || !pt16)) || ids_cap < 0 || (ids_cap > 0 && !ids))
+        return EPP_ERR_INVALID_ARGUMENT;
+    epp::HostWorld hw;
+    hw.r_gate = r_gate;
+    hw.r_obst = r_obst;
+    if (!epp::build_blob(hw, obbs, n)) return EPP_ERR_UNSUPPORTED;
+    const epp::WorldView& v = hw.view;
+    const char* b = hw.blob.data();
+    int64_t n_ids = 0;  // the end of the last list
+    for (uint32_t l = 0; l < v.n_lists; ++l) {
+        uint32_t h;
+        std::memcpy(&h, b + v.off_lists + 4 * (size_t)l, 4);
+        n_ids = std::max<int64_t>(n_ids, (int64_t)(h >> 12) + (h & 4095u));
+    }
+    if (n > 0) std::memcpy(recs17, b + v.off_aos, (size_t)n * epp::kRecDoubles * 8);
+    for (int i = 0; i < n; ++i)
+        for (uint32_t c = 0; c < 8; ++c)
+            std::memcpy(pt16 + (size_t)i * epp::kPtDoubles + 2 * c, b + v.off_pt + epp::pt_chunk_off((uint32_t)i, c), 16);
+    if (ids_cap > 0) std::memcpy(ids, b + v.off_ids, (size_t)std::min<int64_t>(ids_cap, n_ids) * 2);
+    const int64_t vals[6] = {v.off_aos, v.off_pt, v.off_lists, v.off_ids, n_ids, v.id_mask};
+    for (int k = 0; k < 6; ++k) out[k] = vals[k];
     return EPP_OK;
 }
 
