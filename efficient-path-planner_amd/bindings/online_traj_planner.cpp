@@ -176,6 +176,36 @@ PYBIND11_MODULE(online_traj_planner, m) {
             py::arg("waypoint_sets"), py::arg("v_max"), py::arg("a_max"), py::arg("sampling_interval"),
             py::arg("min_distance"))
         .def(
+            "sweep_candidate_trajectories",  // the same plus the chords between the rows (this build)
+            [](const epp::PathPlanner& self, const std::vector<py::object>& waypointSets, double vMax, double aMax,
+               double samplingInterval, double minDistance, bool canPassGate) {
+                std::vector<std::vector<Vec3>> sets;
+                for (const auto& o : waypointSets) {
+                    Matrix w = to_matrix(o);
+                    if (w.cols != 3) throw std::invalid_argument("waypoints must be an (n, 3) array");
+                    std::vector<Vec3> wp;
+                    for (size_t i = 0; i < w.rows; ++i) wp.emplace_back(w(i, 0), w(i, 1), w(i, 2));
+                    sets.push_back(std::move(wp));
+                }
+                std::vector<long> rows, chords;
+                std::vector<double> times;
+                {
+                    py::gil_scoped_release release;
+                    self.sweepCandidateTrajectories(sets, vMax, aMax, samplingInterval, minDistance, canPassGate, rows,
+                                                    chords, &times);
+                }
+                py::array_t<int64_t> r((py::ssize_t)rows.size()), c((py::ssize_t)chords.size());
+                py::array_t<double> t((py::ssize_t)times.size());
+                for (size_t i = 0; i < rows.size(); ++i) {
+                    r.mutable_data()[i] = rows[i];
+                    c.mutable_data()[i] = chords[i];
+                    t.mutable_data()[i] = times[i];
+                }
+                return py::make_tuple(r, c, t);
+            },
+            py::arg("waypoint_sets"), py::arg("v_max"), py::arg("a_max"), py::arg("sampling_interval"),
+            py::arg("min_distance"), py::arg("can_pass_gate") = false)
+        .def(
             "check_point_validity",
             [](const epp::PathPlanner& self, const py::object& p, bool canPassGate) {
                 return self.worldPtr->checkPointValidity(to_vec3(p), canPassGate);

@@ -1490,17 +1490,25 @@ bool PathPlanner::checkTrajectoryValidityAndGenerate(const Matrix& traj, double 
     return true;
 }
 
-bool PathPlanner::checkCandidateTrajectories(const std::vector<std::vector<Vec3>>& sets, double v_max, double a_max,
-                                             double dt, double minDistance, std::vector<long>& firstInvalidRow,
-                                             std::vector<double>* firstInvalidTime) const {
+namespace {
+// The fit of every waypoint set (epp_minsnap_batch) and, on the same device buffers and
+// stream, the first failing row (epp_traj_check_batch) and -- chords != nullptr -- the first
+// failing chord (epp_traj_sweep_batch) of every fitted track; one synchronisation, at the end.
+// `what` names the caller in the errors.
+void fit_and_check_candidates(const char* what, const epp_world* world, const std::vector<std::vector<Vec3>>& sets,
+                              double v_max, double a_max, double dt, double minDistance, int32_t canPassGate,
+                              std::vector<long>& firstInvalidRow, std::vector<double>* rowTimes,
+                              std::vector<long>* chords, std::vector<double>* chordTimes) {
     for (const auto& s : sets)
         if (s.size() < 2) throw std::invalid_argument("At least two waypoints are required");
     const size_t n = sets.size();
     firstInvalidRow.assign(n, -1);
-    if (firstInvalidTime) firstInvalidTime->assign(n, -1.0);
-    if (n == 0) return true;
+    if (rowTimes) rowTimes->assign(n, -1.0);
+    if (chords) chords->assign(n, -1);
+    if (chordTimes) chordTimes->assign(n, -1.0);
+    if (n == 0) return;
     // host image of the upload: [waypoints | offsets]; device block: [wp | T | coeffs |
-    // first_time | first_invalid | offsets | status]
+    // first_time | first_invalid | chord_time | chord | offsets | status]
     size_t total = 0;
     for (const auto& s : sets) total += s.size();
     const size_t nseg = total - n;
@@ -1524,14 +1532,14 @@ bool PathPlanner::checkCandidateTrajectories(const std::vector<std::vector<Vec3>
             if (buf) (void)epp_free(buf);
         }
     } d;
-    auto need = [](epp_status rc) {
+    auto need = [what](epp_status rc) {
         if (rc == EPP_ERR_INVALID_ARGUMENT) throw std::invalid_argument(epp_last_error());
-        if (rc != EPP_OK) throw std::runtime_error(std::string("checkCandidateTrajectories: ") + epp_last_error());
+        if (rc != EPP_OK) throw std::runtime_error(std::string(what) + ": " + epp_last_error());
     };
     auto after = [](size_t o, size_t b) { return (o + b + 255) & ~(size_t)255; };  // 256-B aligned parts
     const size_t o_wp = 0, o_T = after(o_wp, total * 24), o_C = after(o_T, nseg * 8), o_ft = after(o_C, nseg * 240),
-                 o_fi = after(o_ft, n * 8), o_off = after(o_fi, n * 8), o_st = after(o_off, (n + 1) * 4),
-                 bytes = after(o_st, n * 4);
+                 o_fi = after(o_ft, n * 8), o_ct = after(o_fi, n * 8), o_ci = after(o_ct, n * 8),
+                 o_off = after(o_ci, n * 8), o_st = after(o_off, (n + 1) * 4), bytes = after(o_st, n * 4);
     need(epp_malloc(&d.buf, bytes));
     need(epp_stream_create(&d.st));
     char* base = static_cast<char*>(d.buf);
@@ -1542,25 +1550,63 @@ bool PathPlanner::checkCandidateTrajectories(const std::vector<std::vector<Vec3>
     const int32_t* d_off = reinterpret_cast<const int32_t*>(base + o_off);
     need(epp_minsnap_batch(reinterpret_cast<const double*>(base + o_wp), d_off, (int32_t)n, v_max, a_max, nullptr,
                            nullptr, d_T, d_C, reinterpret_cast<int32_t*>(base + o_st), d.st));
-    need(epp_traj_check_batch(worldPtr->device(), d_T, d_C, d_off, (int32_t)n, dt, minDistance,
+    need(epp_traj_check_batch(world, d_T, d_C, d_off, (int32_t)n, dt, minDistance,
                               reinterpret_cast<int64_t*>(base + o_fi), reinterpret_cast<double*>(base + o_ft), d.st));
+    if (chords)
+        need(epp_traj_sweep_batch(world, d_T, d_C, d_off, (int32_t)n, dt, canPassGate,
+                                  reinterpret_cast<int64_t*>(base + o_ci), reinterpret_cast<double*>(base + o_ct),
+                                  d.st));
     std::vector<int32_t> status(n);
-    std::vector<int64_t> rows(n);
-    std::vector<double> times(n);
+    std::vector<int64_t> rows(n), crows(n);
+    std::vector<double> times(n), ctimes(n);
     need(epp_memcpy_d2h_async(status.data(), base + o_st, n * 4, d.st));
     need(epp_memcpy_d2h_async(rows.data(), base + o_fi, n * 8, d.st));
     need(epp_memcpy_d2h_async(times.data(), base + o_ft, n * 8, d.st));
+    if (chords) {
+        need(epp_memcpy_d2h_async(crows.data(), base + o_ci, n * 8, d.st));
+        need(epp_memcpy_d2h_async(ctimes.data(), base + o_ct, n * 8, d.st));
+    }
     need(epp_stream_sync(d.st));
     for (size_t k = 0; k < n; ++k)
         if (status[k] != 0)
             throw std::runtime_error("generateTrajectory: the fit of waypoint set " + std::to_string(k) +
                                      " failed (status " + std::to_string(status[k]) + ")");
-    bool all = true;
     for (size_t k = 0; k < n; ++k) {
         firstInvalidRow[k] = (long)rows[k];
-        all = all && rows[k] < 0;
+        if (chords) (*chords)[k] = (long)crows[k];
     }
-    if (firstInvalidTime) *firstInvalidTime = times;
+    if (rowTimes) *rowTimes = times;
+    if (chords && chordTimes) *chordTimes = ctimes;
+}
+}  // namespace
+
+bool PathPlanner::checkCandidateTrajectories(const std::vector<std::vector<Vec3>>& sets, double v_max, double a_max,
+                                             double dt, double minDistance, std::vector<long>& firstInvalidRow,
+                                             std::vector<double>* firstInvalidTime) const {
+    fit_and_check_candidates("checkCandidateTrajectories", sets.empty() ? nullptr : worldPtr->device(), sets, v_max,
+                             a_max, dt, minDistance, 0, firstInvalidRow, firstInvalidTime, nullptr, nullptr);
+    for (long r : firstInvalidRow)
+        if (r >= 0) return false;
+    return true;
+}
+
+bool PathPlanner::sweepCandidateTrajectories(const std::vector<std::vector<Vec3>>& sets, double v_max, double a_max,
+                                             double dt, double minDistance, bool canPassGate,
+                                             std::vector<long>& firstInvalidRow, std::vector<long>& firstInvalidChord,
+                                             std::vector<double>* firstInvalidTime) const {
+    std::vector<double> rowTimes, chordTimes;
+    fit_and_check_candidates("sweepCandidateTrajectories", sets.empty() ? nullptr : worldPtr->device(), sets, v_max,
+                             a_max, dt, minDistance, canPassGate ? 1 : 0, firstInvalidRow, &rowTimes,
+                             &firstInvalidChord, &chordTimes);
+    bool all = true;
+    if (firstInvalidTime) firstInvalidTime->assign(sets.size(), -1.0);
+    for (size_t k = 0; k < sets.size(); ++k) {
+        const long r = firstInvalidRow[k], c = firstInvalidChord[k];
+        all = all && r < 0 && c < 0;
+        // the earlier of the two findings (a failing row j and a failing chord j start at the same time)
+        if (firstInvalidTime && (r >= 0 || c >= 0))
+            (*firstInvalidTime)[k] = (c < 0 || (r >= 0 && r <= c)) ? rowTimes[k] : chordTimes[k];
+    }
     return all;
 }
 

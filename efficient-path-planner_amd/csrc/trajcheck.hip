@@ -166,6 +166,136 @@ __global__ __launch_bounds__(kTcBlock) void k_traj_check(WorldView w, const doub
     }
 }
 
+// ---- k_traj_sweep: the chords between consecutive rows ---------------------------------
+//   World::checkRayValid(p_j, p_j+1, canPassGate)  src/World.cpp:130-162, for the rows p_j of
+//   Trajectory::evaluateRange(0, max_time, dt); the answer per track is the lowest j whose
+//   chord fails: epp_sample_batch + epp_check_motions (mode 0) on consecutive rows.
+//
+// k_traj_check's shape (thread 0 runs the recurrence a chunk ahead, wave 1 checks the other
+// half, one barrier per chunk).  A checking lane takes G = ceil(cnt / 64) consecutive samples
+// of the chunk (8 of a full one) and tests the chords that END at them, so every chord has one
+// owner: the chord into a lane's first sample starts at the last sample of the lane before
+// it, which that lane evaluates first and hands up (one ds_bpermute shift per coordinate);
+// lane 0 takes the previous chunk's last position, carried in a register of wave 1 (lane
+// 63's, broadcast).  Every position is evaluated once; the track's first row ends no chord.
+// The ray test is ray_valid (collision_common.h), the generic motion kernel's scalar walk: it
+// reads cell starts, cell lists, meta words and the SoA table; everything before the table is
+// staged in LDS when it fits (kTsWorldLds), else only the front, else nothing.
+// LDS result word of a half: the lowest failing chord's END sample in the half (0: the chord
+// from the previous chunk); its time is the START row's, which for 0 lies in the half the
+// producer is overwriting: thread 0 keeps it (prev_tac) before it produces.
+constexpr uint32_t kTsWorldLds = 24 * 1024;
+
+// STAGE: 0 nothing staged, 1 the front (cell starts), 2 the blob up to the SoA table (cell
+// starts, cell lists, meta words)
+template <int STAGE>
+__global__ __launch_bounds__(kTcBlock) void k_traj_sweep(WorldView w, const double* __restrict__ seg_times,
+                                                         const double* __restrict__ coeffs,
+                                                         const int32_t* __restrict__ wp_off, int n_tracks, double dt,
+                                                         int can_pass, int64_t* __restrict__ first_invalid,
+                                                         double* __restrict__ first_time, uint32_t stage_bytes) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    TcShared& s = *reinterpret_cast<TcShared*>(lds);
+    const unsigned char* staged = STAGE ? stage_world(w, lds + kTcSharedBytes, stage_bytes) : w.blob;
+    Acc a = make_acc(staged, w.blob, w);
+    if (STAGE == 2) {
+        a.meta = reinterpret_cast<const uint32_t*>(staged + w.off_meta);
+        a.co = reinterpret_cast<const uint16_t*>(staged + w.off_cell_obb);
+    }
+    const int tid = threadIdx.x;
+    const bool producer = tid < 64;
+    const bool cp = can_pass != 0;
+    RangeIter it;  // (thread 0's)
+    for (int t = blockIdx.x; t < n_tracks; t += gridDim.x) {
+        const int w0 = wp_off[t];
+        const int M = wp_off[t + 1] - w0 - 1;
+        int64_t res = -1;  // no chord fails (also: fewer than two rows)
+        double rtime = -1.0;
+        if (M >= 1) {  // (workgroup-uniform)
+            const int seg0 = w0 - t;
+            const double* Tg = seg_times + seg0;
+            const bool t_lds = M <= kTcSegLds;
+            __syncthreads();  // the previous track's reads of s are over
+            if (t_lds)
+                for (int i = tid; i < M; i += kTcBlock) s.T[i] = Tg[i];
+            __syncthreads();
+            if (tid == 0) {
+                it.init(t_lds ? s.T : Tg, M);
+                tc_produce(it, s, 0, dt);
+            }
+            __syncthreads();
+            int64_t base = 0;
+            int b = 0;
+            double cx = 0.0, cy = 0.0, cz = 0.0;  // wave 1: the previous chunk's last position
+            double prev_tac = 0.0;                // thread 0: the previous chunk's last time
+            auto pos = [&](int j, double (&p)[3]) {
+                const double* cs = coeffs + (size_t)(seg0 + s.seg[b][j]) * (3 * kPolyCoeffs);
+                const double tin = s.tin[b][j];
+                p[0] = poly_eval_pos(cs, tin);
+                p[1] = poly_eval_pos(cs + kPolyCoeffs, tin);
+                p[2] = poly_eval_pos(cs + 2 * kPolyCoeffs, tin);
+            };
+            // (the barrier and the ordering of the LDS accesses around it: as in k_traj_check)
+            for (;;) {
+                const int cnt = s.cnt[b], done = s.done[b];
+                if (producer) {
+                    if (tid == 0) {
+                        const double last = s.tac[b ^ 1][kRowChunk - 1];  // (unused before the second chunk)
+                        if (!done) tc_produce(it, s, b ^ 1, dt);  // the next chunk meanwhile
+                        prev_tac = last;
+                    }
+                } else {
+                    const int lane = tid - 64;
+                    const int G = (cnt + kTcCheckers - 1) / kTcCheckers;
+                    const int j0 = lane * G;
+                    const int j1 = min(j0 + G, cnt);
+                    const bool has = j0 < cnt;
+                    double l[3] = {0.0, 0.0, 0.0};  // the lane's last sample
+                    if (has) pos(j1 - 1, l);
+                    // (whole wave: no lane has left the loop; a lane without samples hands up
+                    // zeros, which only a lane without samples receives)
+                    double q[3] = {__shfl_up(l[0], 1), __shfl_up(l[1], 1), __shfl_up(l[2], 1)};
+                    if (lane == 0) {
+                        q[0] = cx;
+                        q[1] = cy;
+                        q[2] = cz;
+                    }
+                    cx = __shfl(l[0], kTcCheckers - 1);  // (a full chunk: sample kRowChunk - 1; else unused)
+                    cy = __shfl(l[1], kTcCheckers - 1);
+                    cz = __shfl(l[2], kTcCheckers - 1);
+                    if (has) {
+                        for (int j = j0; j < j1; ++j) {
+                            double e[3] = {l[0], l[1], l[2]};
+                            if (j < j1 - 1) pos(j, e);
+                            if ((base | j) != 0 && !ray_valid(a, w, q, e, cp)) {  // (row 0 ends no chord)
+                                atomicMin(&s.first[b], j);  // (a lane's chords ascend: its first failure is its lowest)
+                                break;
+                            }
+                            q[0] = e[0];
+                            q[1] = e[1];
+                            q[2] = e[2];
+                        }
+                    }
+                }
+                __syncthreads();
+                const int f = s.first[b];
+                if (f != INT_MAX) {
+                    res = base + f - 1;  // the chord's start row
+                    rtime = (f > 0 ? s.tac[b][f - 1] : prev_tac) + 0.0;  // epp_sample_batch's time column with t0 == NULL
+                    break;
+                }
+                if (done) break;
+                base += cnt;
+                b ^= 1;
+            }
+        }
+        if (tid == 0) {
+            first_invalid[t] = res;
+            if (first_time) first_time[t] = rtime;
+        }
+    }
+}
+
 }  // namespace
 }  // namespace epp
 
@@ -199,6 +329,48 @@ epp_status epp_traj_check_batch(const epp_world* world, const double* seg_times,
         hipLaunchKernelGGL((k_traj_check<false>), dim3(grid), dim3(kTcBlock), shm, (hipStream_t)stream, v, seg_times,
                            coeffs, wp_offsets, n_tracks, dt, min_distance, first_invalid, first_time, 0u);
     return launch_error("epp_traj_check_batch");
+}
+
+epp_status epp_traj_sweep_batch(const epp_world* world, const double* seg_times, const double* coeffs,
+                                const int32_t* wp_offsets, int32_t n_tracks, double dt, int32_t can_pass_gate,
+                                int64_t* first_invalid, double* first_time, void* stream) {
+    if (!world || n_tracks < 0 || !(dt > 0) || !std::isfinite(dt) || (can_pass_gate != 0 && can_pass_gate != 1) ||
+        (n_tracks > 0 && (!seg_times || !coeffs || !wp_offsets || !first_invalid))) {
+        set_error("epp_traj_sweep_batch: invalid argument");
+        return EPP_ERR_INVALID_ARGUMENT;
+    }
+    if (n_tracks == 0) return EPP_OK;
+    IndexLease ix;  // (a stale index is rebuilt here, as by epp_check_motions)
+    if (const epp_status st = ensure_index(world, &ix)) return st;
+    const WorldView& v = ix.view;
+    // What the ray walk reads short of the SoA table (cell starts, cell lists, meta words) in
+    // LDS when it fits, else the front alone, else nothing.  EPP_TRAJSWEEP_STAGE = 0 | 1 caps
+    // the level (A/B and test knob): 0 reads the whole world through L2.
+    const int cap = env_int("EPP_TRAJSWEEP_STAGE", 2);
+    int level = 0;
+    uint32_t bytes = 0;
+    if (cap >= 2 && v.off_soa % 16 == 0 && v.off_soa <= kTsWorldLds) {
+        level = 2;
+        bytes = v.off_soa;
+    } else if (cap >= 1 && v.front_bytes <= kTsWorldLds) {
+        level = 1;
+        bytes = v.front_bytes;
+    }
+    const uint32_t shm = kTcSharedBytes + bytes;
+    // persistent grid: the workgroups that stay resident (2 waves each; 8 per CU, fewer by LDS)
+    const int per_cu = std::max(1, std::min<int>(8, (int)((160u * 1024u) / shm)));
+    const int grid = (int)std::min<int64_t>(n_tracks, (int64_t)cu_count() * per_cu);
+#define EPP_LAUNCH_TS(LEVEL)                                                                                       \
+    hipLaunchKernelGGL((k_traj_sweep<LEVEL>), dim3(grid), dim3(kTcBlock), shm, (hipStream_t)stream, v, seg_times, \
+                       coeffs, wp_offsets, n_tracks, dt, can_pass_gate, first_invalid, first_time, bytes)
+    if (level == 2)
+        EPP_LAUNCH_TS(2);
+    else if (level == 1)
+        EPP_LAUNCH_TS(1);
+    else
+        EPP_LAUNCH_TS(0);
+#undef EPP_LAUNCH_TS
+    return launch_error("epp_traj_sweep_batch");
 }
 
 }  // extern "C"

@@ -96,6 +96,7 @@ def lib() -> C.CDLL:
             "epp_traj_peaks": (i32, [vp, vp, vp, i32, vp, vp, vp]),
             "epp_traj_scale_to_limits": (i32, [vp, vp, vp, i32, dp, dp, vp, vp, vp]),
             "epp_traj_check_batch": (i32, [vp, vp, vp, vp, i32, dp, dp, vp, vp, vp]),
+            "epp_traj_sweep_batch": (i32, [vp, vp, vp, vp, i32, dp, i32, vp, vp, vp]),
             "epp_generate_trajectory_limited_host": (i32, [vp, i32, dp, dp, dp, dp, vp, vp,
                                                            C.POINTER(C.POINTER(C.c_double)), C.POINTER(i64),
                                                            C.POINTER(C.c_double)]),
@@ -155,7 +156,7 @@ EXPORTED = [
     "epp_comm_allreduce_f64", "epp_comm_barrier", "epp_comm_available", "epp_knn_ws_box", "epp_knn_grid_ws_box",
     "epp_comm_set_timeout", "epp_comm_abort", "epp_check_and_generate_trajectory_host",
     "epp_traj_peaks", "epp_traj_scale_to_limits", "epp_generate_trajectory_limited_host",
-    "epp_traj_check_batch",
+    "epp_traj_check_batch", "epp_traj_sweep_batch",
 ]
 
 
@@ -329,6 +330,19 @@ class World:
         d_row, d_time = DeviceBuffer(8 * nt), DeviceBuffer(8 * nt)
         check(lib().epp_traj_check_batch(self.handle, d_T.ptr, d_C.ptr, d_off.ptr, nt, float(dt), float(min_distance),
                                          d_row.ptr, d_time.ptr, None))
+        sync()
+        return d_row.download(np.int64, nt), d_time.download(np.float64, nt)
+
+    def sweep_trajectories(self, Ts, Cs, dt: float, can_pass_gate: bool = False):
+        """epp_traj_sweep_batch on the lists minsnap_batch returns: per track the index j of the
+        first chord row j -> row j + 1 (rows of Trajectory::evaluateRange at dt) that fails
+        World::checkRayValid and row j's time, (-1, -1.0) when no chord fails.  Returns
+        (int64[n], float64[n])."""
+        nt = len(Ts)
+        d_T, d_C, d_off, _, _ = _upload_tracks(Ts, Cs)
+        d_row, d_time = DeviceBuffer(8 * nt), DeviceBuffer(8 * nt)
+        check(lib().epp_traj_sweep_batch(self.handle, d_T.ptr, d_C.ptr, d_off.ptr, nt, float(dt),
+                                         1 if can_pass_gate else 0, d_row.ptr, d_time.ptr, None))
         sync()
         return d_row.download(np.int64, nt), d_time.download(np.float64, nt)
 

@@ -32,6 +32,9 @@
  *   epp_traj_check_batch
  *       PathPlanner::checkTrajectoryValidity (src/PathPlanner.cpp:267-280) of every fitted
  *       track, from its coefficients: the first failing row per track.
+ *   epp_traj_sweep_batch
+ *       World::checkRayValid (src/World.cpp:130-162) on the chords between consecutive rows
+ *       of every fitted track: the first failing chord per track.
  */
 #ifndef EPP_H_
 #define EPP_H_
@@ -236,6 +239,26 @@ epp_status epp_traj_scale_to_limits(double* seg_times, double* coeffs, const int
  * first_invalid with n_tracks > 0; n_tracks == 0 launches nothing. */
 epp_status epp_traj_check_batch(const epp_world* w, const double* seg_times, const double* coeffs,
                                 const int32_t* wp_offsets, int32_t n_tracks, double dt, double min_distance,
+                                int64_t* first_invalid, double* first_time, void* stream);
+/* The swept companion of epp_traj_check_batch (same layout, same contract): the rows only
+ * say where the track is every dt, this call tests the straight chords between them.  With
+ * p_0 .. p_{R-1} the positions of the rows of Trajectory::evaluateRange(0, max_time, dt) of
+ * track k, chord j (0 <= j < R - 1) is p_j -> p_{j+1}, tested with World::checkRayValid(p_j,
+ * p_{j+1}, can_pass_gate) (src/World.cpp:130-162; epp_check_motions mode 0).
+ * first_invalid[k] (n_tracks, device int64) is the smallest j whose chord fails, -1 if none
+ * does; first_time[k] (n_tracks, device f64, may be NULL) is the time column of row j as
+ * epp_sample_batch writes it with t0 == NULL, -1.0 if none fails.  A track with fewer than
+ * two rows (one waypoint, the NaN times of a failed fit) has no chord: -1 / -1.0.  The
+ * answers are those of epp_sample_count + epp_sample_batch + epp_check_motions(s1 = rows j,
+ * s2 = rows j + 1, columns 0 / 3 / 6, mode 0) per track, bit for bit (the same recurrence,
+ * Horner steps and predicates; a zero-length chord takes the ray test's |d| < 1e-6 branches
+ * as there).  Stream-ordered, no host synchronisation and no allocation; a stale world
+ * index is rebuilt first, so the call can be captured after epp_world_build_index.
+ * EPP_ERR_INVALID_ARGUMENT (before any device work) for a NULL world, n_tracks < 0, dt <= 0
+ * or not finite, can_pass_gate not 0 or 1, or a NULL seg_times, coeffs, wp_offsets or
+ * first_invalid with n_tracks > 0; n_tracks == 0 launches nothing. */
+epp_status epp_traj_sweep_batch(const epp_world* w, const double* seg_times, const double* coeffs,
+                                const int32_t* wp_offsets, int32_t n_tracks, double dt, int32_t can_pass_gate,
                                 int64_t* first_invalid, double* first_time, void* stream);
 
 /* ---- batch planner building blocks (device pointers) ------------------------------- */

@@ -119,6 +119,19 @@ public:
     bool checkCandidateTrajectories(const std::vector<std::vector<Vec3>>& waypointSets, double v_max, double a_max,
                                     double dt, double minDistance, std::vector<long>& firstInvalidRow,
                                     std::vector<double>* firstInvalidTime = nullptr) const;
+    // checkCandidateTrajectories plus the swept check of the same fits (an addition of this
+    // build): the rows only say where a track is every dt, so a track faster than a bar is
+    // thick can step over it; the straight chords between consecutive rows are therefore
+    // tested too, with World::checkRayValid(p_j, p_j+1, canPassGate) (epp_traj_sweep_batch),
+    // on the same fitted batch and stream, synchronising once.  firstInvalidRow[k]: as
+    // checkCandidateTrajectories; firstInvalidChord[k]: the smallest j whose chord row j ->
+    // row j + 1 fails, -1 if none; firstInvalidTime (optional): the time of the earlier of the
+    // two findings (row j and chord j both start at row j's time), -1.0 if neither.  Returns
+    // true iff no row and no chord of any set fails.  Throws as checkCandidateTrajectories.
+    bool sweepCandidateTrajectories(const std::vector<std::vector<Vec3>>& waypointSets, double v_max, double a_max,
+                                    double dt, double minDistance, bool canPassGate,
+                                    std::vector<long>& firstInvalidRow, std::vector<long>& firstInvalidChord,
+                                    std::vector<double>* firstInvalidTime = nullptr) const;
     std::vector<Vec3> includeGates2(std::vector<std::vector<Vec3>> waypoints) const;
     // planPaths of consecutive gate-to-gate segments, then includeGates2 of their paths (an
     // addition of this build, for OnlineTrajGenerator::preComputeTraj): the same answers as

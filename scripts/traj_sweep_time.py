@@ -1,0 +1,157 @@
+#!/usr/bin/env python3
+"""Device time of the fused swept check (epp_traj_sweep_batch: the chords between consecutive
+rows through World::checkRayValid) beside the composition it replaces, on 4096 fitted tracks of
+12 segments (seeds 10_000 + k, v_max = 1.0, a_max = 2.0) sampled at dt = 0.01 against the
+72-OBB world (synth.track_world(42), configs/config_filling.json), can_pass_gate = 0:
+
+    fused      epp_traj_sweep_batch: one launch, no row written
+    composed   epp_sample_count + epp_sample_batch (80 B per row to HBM) + epp_check_motions
+               (mode 0) on the two contiguous n x 3 edge arrays of consecutive positions
+               (the repack itself, a host step today, is made once outside the timing)
+
+in two cases: "valid" (every track lifted 10 m, above every obstacle: no early exit, every row
+evaluated and every chord tested) and "mixed" (the tracks as fitted).
+
+hipEvent pairs on one stream around each call, --warmup untimed launches, then --reps timed
+ones; median, min and max of each, the three composed calls timed one by one and summed (each
+of the two sampling calls reads the track offsets back inside its pair, as it always does).
+
+    python scripts/traj_sweep_time.py [--reps 20] [--out profiles/traj_sweep_time.json]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "efficient-path-planner_amd"))
+
+from eppamd import capi, config, synth  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--tracks", type=int, default=4096)
+    ap.add_argument("--dt", type=float, default=0.01)
+    ap.add_argument("--can-pass-gate", type=int, default=0)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    L = capi.lib()
+    nt, dt, cp = a.tracks, a.dt, a.can_pass_gate
+    cfg = config.load(os.path.join(ROOT, "configs", "config_filling.json"))
+    rg, ro = config.inflate_radii(cfg)
+    world = capi.World(capi.build_obbs(config.geometry(cfg), *synth.track_world(42)), rg, ro)
+    world.build_index()
+    stream = C.c_void_p()
+    capi.check(L.epp_stream_create(C.byref(stream)))
+    ev = [C.c_void_p(), C.c_void_p()]
+    for e in ev:
+        capi.check(L.epp_event_create(C.byref(e)))
+    off = np.arange(nt + 1, dtype=np.int32) * 13
+    d_off = capi.DeviceBuffer.from_array(off, stream)
+    d_T, d_C = capi.DeviceBuffer(8 * 12 * nt), capi.DeviceBuffer(240 * 12 * nt)
+    d_st, d_cnt, d_roff = capi.DeviceBuffer(4 * nt), capi.DeviceBuffer(8 * nt), capi.DeviceBuffer(8 * nt)
+    d_first, d_time = capi.DeviceBuffer(8 * nt), capi.DeviceBuffer(8 * nt)
+
+    def timed(fn):
+        ms = []
+        for r in range(a.warmup + a.reps):
+            capi.check(L.epp_event_record(ev[0], stream))
+            fn()
+            capi.check(L.epp_event_record(ev[1], stream))
+            capi.check(L.epp_stream_sync(stream))
+            x = C.c_float(0)
+            capi.check(L.epp_event_elapsed_ms(ev[0], ev[1], C.byref(x)))
+            if r >= a.warmup:
+                ms.append(x.value)
+        ms = np.array(ms)
+        return {"median_ms": float(np.median(ms)), "min_ms": float(ms.min()), "max_ms": float(ms.max())}
+
+    res = {"tracks": nt, "segments": 12, "dt": dt, "can_pass_gate": cp, "obbs": world.n, "reps": a.reps,
+           "warmup": a.warmup}
+    for case, lift in (("valid", 10.0), ("mixed", 0.0)):
+        tracks = [synth.random_track_waypoints(10_000 + k, 12) + [0.0, 0.0, lift] for k in range(nt)]
+        d_wp = capi.DeviceBuffer.from_array(np.ascontiguousarray(np.concatenate(tracks)), stream)
+        capi.check(L.epp_minsnap_batch(d_wp.ptr, d_off.ptr, nt, 1.0, 2.0, None, None, d_T.ptr, d_C.ptr, d_st.ptr,
+                                       stream))
+        capi.check(L.epp_stream_sync(stream))
+        assert (d_st.download(np.int32, nt, stream) == 0).all()
+
+        def count():
+            capi.check(L.epp_sample_count(d_T.ptr, d_off.ptr, nt, dt, d_cnt.ptr, stream))
+
+        count()
+        capi.check(L.epp_stream_sync(stream))
+        cnt = d_cnt.download(np.int64, nt, stream)
+        roff = np.zeros(nt + 1, np.int64)
+        roff[1:] = np.cumsum(cnt)
+        n_rows = int(roff[-1])
+        d_roff.upload(roff[:-1].copy(), stream)
+        d_rows = capi.DeviceBuffer(80 * n_rows)
+
+        def rows():
+            capi.check(L.epp_sample_batch(d_T.ptr, d_C.ptr, d_off.ptr, nt, dt, None, d_roff.ptr, d_rows.ptr, stream))
+
+        rows()
+        capi.check(L.epp_stream_sync(stream))
+        host_rows = d_rows.download(np.float64, n_rows * 10, stream).reshape(-1, 10)
+        # the repack (untimed): chord j of track k runs from row j to row j + 1 of that track
+        start = np.ones(n_rows, bool)
+        start[roff[1:][cnt > 0] - 1] = False  # a track's last row starts no chord
+        si = np.flatnonzero(start)
+        n_ch = len(si)
+        coff = np.zeros(nt + 1, np.int64)
+        coff[1:] = np.cumsum(np.maximum(cnt - 1, 0))
+        xyz = host_rows[:, [0, 3, 6]]
+        d_s1 = capi.DeviceBuffer.from_array(np.ascontiguousarray(xyz[si]), stream)
+        d_s2 = capi.DeviceBuffer.from_array(np.ascontiguousarray(xyz[si + 1]), stream)
+        d_valid = capi.DeviceBuffer(n_ch)
+
+        def motions():
+            capi.check(L.epp_check_motions(world.handle, d_s1.ptr, d_s2.ptr, n_ch, cp, 0, d_valid.ptr, stream))
+
+        def fused():
+            capi.check(L.epp_traj_sweep_batch(world.handle, d_T.ptr, d_C.ptr, d_off.ptr, nt, dt, cp, d_first.ptr,
+                                              d_time.ptr, stream))
+
+        r = {"rows": n_rows, "chords": n_ch}
+        print(f"{case}: {n_rows} rows, {n_ch} chords uploaded; timing", file=sys.stderr, flush=True)
+        r["fused"] = timed(fused)
+        r["sample_count"] = timed(count)
+        r["sample_batch"] = timed(rows)
+        r["check_motions"] = timed(motions)
+        parts = ("sample_count", "sample_batch", "check_motions")
+        r["composed"] = {k: float(sum(r[p][k] for p in parts)) for k in ("median_ms", "min_ms", "max_ms")}
+        r["composed_over_fused"] = r["composed"]["median_ms"] / r["fused"]["median_ms"]
+        # the same answers, or the times compare different work
+        first = d_first.download(np.int64, nt, stream)
+        flags = d_valid.download(np.uint8, n_ch, stream)
+        exp = np.full(nt, -1, np.int64)
+        bad = np.flatnonzero(flags == 0)
+        tr = np.searchsorted(coff, bad, side="right") - 1
+        uniq, idx = np.unique(tr, return_index=True)
+        exp[uniq] = bad[idx] - coff[uniq]
+        assert np.array_equal(first, exp), "fused and composed answers differ"
+        r["tracks_valid"] = int((first < 0).sum())
+        r["chords_before_first_collision"] = int(np.where(first < 0, np.maximum(cnt - 1, 0), first + 1).sum())
+        res[case] = r
+        for b in (d_rows, d_s1, d_s2, d_valid, d_wp):
+            b.free()
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    for e in ev:
+        L.epp_event_destroy(e)
+    capi.check(L.epp_stream_destroy(stream))
+
+
+if __name__ == "__main__":
+    main()
