@@ -561,19 +561,7 @@ __global__ __launch_bounds__(kWave) void k_sample_count(const double* __restrict
     if (threadIdx.x == 0) {
         RangeIter it;
         it.init(sT, M);
-        int64_t n = 0;
-        int seg;
-        double tin, tac, tin8[8], tac8[8];
-        for (;;) {
-            if (it.fast8(dt, tin8, tac8)) {
-                n += 8;
-                continue;
-            }
-            if (!it.next(seg, tin, tac)) break;
-            ++n;
-            it.advance(dt);
-        }
-        counts[t] = n;
+        counts[t] = range_count(it, dt);
     }
 }
 
@@ -613,33 +601,7 @@ __global__ __launch_bounds__(kWave) void k_sample_rows(const double* __restrict_
     }
     int64_t base = 0;
     while (true) {
-        if (lane == 0) {
-            int c = 0;
-            int seg;
-            double tin, tac, tin8[8], tac8[8];
-            while (c < kRowChunk) {
-                if (c + 8 <= kRowChunk && it.fast8(dt, tin8, tac8)) {
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) {
-                        s_seg[c + k] = it.i;
-                        s_tin[c + k] = tin8[k];
-                        s_tac[c + k] = tac8[k];
-                    }
-                    c += 8;
-                    continue;
-                }
-                if (!it.next(seg, tin, tac)) {
-                    s_done = 1;
-                    break;
-                }
-                s_seg[c] = seg;
-                s_tin[c] = tin;
-                s_tac[c] = tac;
-                ++c;
-                it.advance(dt);
-            }
-            s_cnt = c;
-        }
+        if (lane == 0) s_cnt = range_produce(it, dt, kRowChunk, s_seg, s_tin, s_tac, s_done);
         __syncthreads();
         const int cnt = s_cnt, done = s_done;
         for (int j = lane; j < cnt && base + j < cap_rows; j += kWave) {  // (cap: single-track host path)
@@ -1138,13 +1100,13 @@ epp_status epp::check_and_generate_into(const FusedCheck* chk, const double* wp,
     if (dt > 0) {
         RangeIter it;
         it.init(c.T.data(), M);
-        int sg;
-        double ti, ta;
-        while (it.next(sg, ti, ta)) {
-            c.seg.push_back(sg);
-            c.tin.push_back(ti);
-            c.tac.push_back(ta);
-            it.advance(dt);
+        int sg[kRowChunk];
+        double ti[kRowChunk], ta[kRowChunk];
+        for (int done = 0; !done;) {
+            const int n = range_produce(it, dt, kRowChunk, sg, ti, ta, done);
+            c.seg.insert(c.seg.end(), sg, sg + n);
+            c.tin.insert(c.tin.end(), ti, ti + n);
+            c.tac.insert(c.tac.end(), ta, ta + n);
         }
     }
     const int R = (int)c.tin.size();
@@ -1416,12 +1378,7 @@ epp_status epp_generate_trajectory_limited_host(const double* wp, int32_t n_wp, 
     if (dt > 0) {  // Trajectory::evaluateRange's recurrence on the scaled times (exact count)
         RangeIter it;
         it.init(h_T, M);
-        int sg;
-        double ti, ta;
-        while (it.next(sg, ti, ta)) {
-            ++R;
-            it.advance(dt);
-        }
+        R = range_count(it, dt);
     }
     double* rows = (double*)std::malloc((size_t)std::max<int64_t>(R, 1) * 80);
     if (!rows) {

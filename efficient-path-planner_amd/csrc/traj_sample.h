@@ -1,7 +1,9 @@
-// traj_sample.h — the sampling arithmetic of a fitted trajectory, shared by the row sampler
-// (minsnap.hip: k_sample_count, k_sample_rows, the host side of the refit) and the fused
-// first-collision check (trajcheck.hip): the evaluateRange time recurrence and the
-// polynomial evaluation.  One definition, so both produce the same sample times, segments
+// traj_sample.h — the sampling arithmetic of a fitted trajectory: the evaluateRange time
+// recurrence (RangeIter), the one loop that steps it (range_produce / range_count) and the
+// polynomial evaluation.  Everything that samples a track runs these: the row sampler
+// (minsnap.hip: k_sample_count, k_sample_rows, the host recurrences of the single-track
+// paths), the fused checks (trajcheck.hip: k_traj_check, k_traj_sweep) and
+// tests/traj_rows_host.cpp.  One definition, so all produce the same sample times, segments
 // and positions bit for bit.  Plain C++ apart from the HIP qualifiers: a host program may
 // include it without the HIP runtime.
 #pragma once
@@ -19,7 +21,7 @@
 namespace epp {
 
 constexpr int kPolyCoeffs = 10;  // coefficients per polynomial (mav_trajectory_generation::Polynomial, N = 10)
-constexpr int kRowChunk = 512;   // samples per k_sample_rows round
+constexpr int kRowChunk = 512;   // samples a kernel's lane 0 produces per round (k_sample_rows, k_traj_*: per LDS half)
 
 // Trajectory::evaluateRange control flow — src/trajectory.cpp:81-141.
 struct RangeIter {
@@ -83,6 +85,55 @@ struct RangeIter {
         return true;
     }
 };
+
+// THE stepping loop of the recurrence: eight samples at once where none rolls over, else
+// one.  ROWS: the next (up to) cap samples into seg / tin / tac (segment, time in the segment,
+// time), the eight only while eight more fit; else every sample left, stored nowhere.
+// Returns how many; sets done to 1 when the recurrence ended, else leaves it alone (a call
+// that fills cap exactly at the end reports the end with the next one, which returns 0).
+template <bool ROWS, class Int>
+EPP_TS_FN Int range_steps(RangeIter& iter, double dt, Int cap, int* seg, double* tin, double* tac, int& done) {
+    RangeIter it = iter;  // (a local copy: the loop keeps it in registers)
+    Int c = 0;
+    int sg;
+    double ti, ta, tin8[8], tac8[8];
+    while (!ROWS || c < cap) {
+        if ((!ROWS || c + 8 <= cap) && it.fast8(dt, tin8, tac8)) {
+            if (ROWS) {
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+                for (int k = 0; k < 8; ++k) {
+                    seg[c + k] = it.i;
+                    tin[c + k] = tin8[k];
+                    tac[c + k] = tac8[k];
+                }
+            }
+            c += 8;
+            continue;
+        }
+        if (!it.next(sg, ti, ta)) {
+            done = 1;
+            break;
+        }
+        if (ROWS) {
+            seg[c] = sg;
+            tin[c] = ti;
+            tac[c] = ta;
+        }
+        ++c;
+        it.advance(dt);
+    }
+    iter = it;
+    return c;
+}
+EPP_TS_FN int range_produce(RangeIter& it, double dt, int cap, int* seg, double* tin, double* tac, int& done) {
+    return range_steps<true>(it, dt, cap, seg, tin, tac, done);
+}
+EPP_TS_FN long long range_count(RangeIter& it, double dt) {
+    int done;
+    return range_steps<false>(it, dt, 0LL, nullptr, nullptr, nullptr, done);
+}
 
 // Polynomial::evaluate(t, k) — polynomial.h:136-149; B: the falling factorials
 // B[k][j] = j! / (j-k)! (src/polynomial.cpp:145-160), row-major 10 x 10

@@ -1,22 +1,27 @@
 #!/usr/bin/env python3
-"""Device time of the fused first-collision check (epp_traj_check_batch) beside the
-composition it replaces, on 4096 fitted tracks of 12 segments (seeds 10_000 + k, v_max = 1.0,
-a_max = 2.0) sampled at dt = 0.01 against the 72-OBB world (synth.track_world(42),
-configs/config_filling.json), min_distance 0.05:
+"""Device time of a fused check of fitted tracks beside the composition it replaces, on 4096
+fitted tracks of 12 segments (seeds 10_000 + k, v_max = 1.0, a_max = 2.0) sampled at dt = 0.01
+against the 72-OBB world (synth.track_world(42), configs/config_filling.json).  --kind:
 
-    fused      epp_traj_check_batch: one launch, no row written
-    composed   epp_sample_count + epp_sample_batch (80 B per row to HBM) +
-               epp_check_states_mindist on the contiguous n x 3 repack of columns 0 / 3 / 6
-               (the repack itself, a host step today, is made once outside the timing)
+    point   epp_traj_check_batch (first failing row, min_distance 0.05) against
+            epp_sample_count + epp_sample_batch (80 B per row to HBM) +
+            epp_check_states_mindist on the contiguous n x 3 repack of columns 0 / 3 / 6
+    chord   epp_traj_sweep_batch (first failing chord between consecutive rows through
+            World::checkRayValid, can_pass_gate 0) against epp_sample_count + epp_sample_batch +
+            epp_check_motions (mode 0) on the two contiguous n x 3 edge arrays of consecutive
+            positions
 
-in two cases: "valid" (every track lifted 10 m, above every obstacle: no early exit, every row
-evaluated and checked) and "mixed" (the tracks as fitted: valid and colliding ones).
+The fused call is one launch and writes no row; the repack of the composed one, a host step
+today, is made once outside the timing.  Two cases: "valid" (every track lifted 10 m, above
+every obstacle: no early exit, everything evaluated and checked) and "mixed" (the tracks as
+fitted: valid and colliding ones).
 
 hipEvent pairs on one stream around each call, --warmup untimed launches, then --reps timed
 ones; median, min and max of each, the three composed calls timed one by one and summed (each
 of the two sampling calls reads the track offsets back inside its pair, as it always does).
 
-    python scripts/traj_check_time.py [--reps 20] [--out profiles/traj_check_time.json]
+    python scripts/traj_fused_time.py --kind point [--reps 20] [--out profiles/traj_check_time.json]
+    python scripts/traj_fused_time.py --kind chord [--reps 20] [--out profiles/traj_sweep_time.json]
 """
 import argparse
 import ctypes as C
@@ -34,15 +39,18 @@ from eppamd import capi, config, synth  # noqa: E402
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--kind", choices=("point", "chord"), required=True)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--tracks", type=int, default=4096)
     ap.add_argument("--dt", type=float, default=0.01)
-    ap.add_argument("--min-distance", type=float, default=0.05)
+    ap.add_argument("--min-distance", type=float, default=0.05, help="point")
+    ap.add_argument("--can-pass-gate", type=int, default=0, help="chord")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     L = capi.lib()
-    nt, dt, md = a.tracks, a.dt, a.min_distance
+    point = a.kind == "point"
+    nt, dt, md, cp = a.tracks, a.dt, a.min_distance, a.can_pass_gate
     cfg = config.load(os.path.join(ROOT, "configs", "config_filling.json"))
     rg, ro = config.inflate_radii(cfg)
     world = capi.World(capi.build_obbs(config.geometry(cfg), *synth.track_world(42)), rg, ro)
@@ -72,8 +80,8 @@ def main():
         ms = np.array(ms)
         return {"median_ms": float(np.median(ms)), "min_ms": float(ms.min()), "max_ms": float(ms.max())}
 
-    res = {"tracks": nt, "segments": 12, "dt": dt, "min_distance": md, "obbs": world.n, "reps": a.reps,
-           "warmup": a.warmup}
+    res = {"tracks": nt, "segments": 12, "dt": dt, **({"min_distance": md} if point else {"can_pass_gate": cp}),
+           "obbs": world.n, "reps": a.reps, "warmup": a.warmup}
     for case, lift in (("valid", 10.0), ("mixed", 0.0)):
         tracks = [synth.random_track_waypoints(10_000 + k, 12) + [0.0, 0.0, lift] for k in range(nt)]
         d_wp = capi.DeviceBuffer.from_array(np.ascontiguousarray(np.concatenate(tracks)), stream)
@@ -92,43 +100,67 @@ def main():
         roff[1:] = np.cumsum(cnt)
         n_rows = int(roff[-1])
         d_roff.upload(roff[:-1].copy(), stream)
-        d_rows, d_xyz, d_valid = capi.DeviceBuffer(80 * n_rows), capi.DeviceBuffer(24 * n_rows), capi.DeviceBuffer(n_rows)
+        d_rows = capi.DeviceBuffer(80 * n_rows)
 
         def rows():
             capi.check(L.epp_sample_batch(d_T.ptr, d_C.ptr, d_off.ptr, nt, dt, None, d_roff.ptr, d_rows.ptr, stream))
 
-        def states():
-            capi.check(L.epp_check_states_mindist(world.handle, d_xyz.ptr, n_rows, md, d_valid.ptr, stream))
-
-        def fused():
-            capi.check(L.epp_traj_check_batch(world.handle, d_T.ptr, d_C.ptr, d_off.ptr, nt, dt, md, d_first.ptr,
-                                              d_time.ptr, stream))
-
         rows()
         capi.check(L.epp_stream_sync(stream))
-        host_rows = d_rows.download(np.float64, n_rows * 10, stream).reshape(-1, 10)
-        d_xyz.upload(np.ascontiguousarray(host_rows[:, [0, 3, 6]]), stream)  # the repack (untimed)
-        r = {"rows": n_rows}
+        xyz = d_rows.download(np.float64, n_rows * 10, stream).reshape(-1, 10)[:, [0, 3, 6]]
+        # the repack (untimed), and where each track's items (rows | chords) start
+        if point:
+            n_items, ioff, per_track = n_rows, roff, cnt
+            d_in = [capi.DeviceBuffer.from_array(np.ascontiguousarray(xyz), stream)]
+        else:  # chord j of track k runs from row j to row j + 1 of that track
+            start = np.ones(n_rows, bool)
+            start[roff[1:][cnt > 0] - 1] = False  # a track's last row starts no chord
+            si = np.flatnonzero(start)
+            n_items, per_track = len(si), np.maximum(cnt - 1, 0)
+            ioff = np.zeros(nt + 1, np.int64)
+            ioff[1:] = np.cumsum(per_track)
+            d_in = [capi.DeviceBuffer.from_array(np.ascontiguousarray(xyz[si + k]), stream) for k in (0, 1)]
+        d_valid = capi.DeviceBuffer(n_items)
+
+        def composed_check():
+            if point:
+                capi.check(L.epp_check_states_mindist(world.handle, d_in[0].ptr, n_items, md, d_valid.ptr, stream))
+            else:
+                capi.check(L.epp_check_motions(world.handle, d_in[0].ptr, d_in[1].ptr, n_items, cp, 0, d_valid.ptr,
+                                               stream))
+
+        def fused():
+            if point:
+                capi.check(L.epp_traj_check_batch(world.handle, d_T.ptr, d_C.ptr, d_off.ptr, nt, dt, md, d_first.ptr,
+                                                  d_time.ptr, stream))
+            else:
+                capi.check(L.epp_traj_sweep_batch(world.handle, d_T.ptr, d_C.ptr, d_off.ptr, nt, dt, cp, d_first.ptr,
+                                                  d_time.ptr, stream))
+
+        check_key = "check_states_mindist" if point else "check_motions"
+        r = {"rows": n_rows} if point else {"rows": n_rows, "chords": n_items}
+        print(f"{case}: {n_rows} rows, {n_items} items uploaded; timing", file=sys.stderr, flush=True)
         r["fused"] = timed(fused)
         r["sample_count"] = timed(count)
         r["sample_batch"] = timed(rows)
-        r["check_states_mindist"] = timed(states)
-        parts = ("sample_count", "sample_batch", "check_states_mindist")
+        r[check_key] = timed(composed_check)
+        parts = ("sample_count", "sample_batch", check_key)
         r["composed"] = {k: float(sum(r[p][k] for p in parts)) for k in ("median_ms", "min_ms", "max_ms")}
         r["composed_over_fused"] = r["composed"]["median_ms"] / r["fused"]["median_ms"]
         # the same answers, or the times compare different work
         first = d_first.download(np.int64, nt, stream)
-        flags = d_valid.download(np.uint8, n_rows, stream)
+        flags = d_valid.download(np.uint8, n_items, stream)
         exp = np.full(nt, -1, np.int64)
         bad = np.flatnonzero(flags == 0)
-        tr = np.searchsorted(roff, bad, side="right") - 1
+        tr = np.searchsorted(ioff, bad, side="right") - 1
         uniq, idx = np.unique(tr, return_index=True)
-        exp[uniq] = bad[idx] - roff[uniq]
+        exp[uniq] = bad[idx] - ioff[uniq]
         assert np.array_equal(first, exp), "fused and composed answers differ"
         r["tracks_valid"] = int((first < 0).sum())
-        r["rows_before_first_collision"] = int(np.where(first < 0, cnt, first + 1).sum())
+        r["rows_before_first_collision" if point else "chords_before_first_collision"] = int(
+            np.where(first < 0, per_track, first + 1).sum())
         res[case] = r
-        for b in (d_rows, d_xyz, d_valid, d_wp):
+        for b in (d_rows, d_valid, d_wp, *d_in):
             b.free()
     line = json.dumps(res)
     print(line)

@@ -23,6 +23,7 @@ import pytest
 
 import oracle as O
 import small_path_inputs as spi
+import trajsweep_inputs as tsi
 from eppamd import capi, synth
 
 from conftest import PKG
@@ -68,8 +69,8 @@ def _fit(name):
     return Ts, Cs
 
 
-def _compose(world, Ts, Cs, dt, md):
-    """The definition: sample count -> rows -> minDistance flags -> first zero per track."""
+def _sample(Ts, Cs, dt):
+    """(rows per track, row offsets, all rows) from epp_sample_count + epp_sample_batch."""
     L = capi.lib()
     nt = len(Ts)
     d_T, d_C, d_off, _, _ = capi._upload_tracks(Ts, Cs)
@@ -84,7 +85,14 @@ def _compose(world, Ts, Cs, dt, md):
     d_rows = capi.DeviceBuffer(80 * max(total, 1))
     capi.check(L.epp_sample_batch(d_T.ptr, d_C.ptr, d_off.ptr, nt, dt, None, d_roff.ptr, d_rows.ptr, None))
     capi.sync()
-    rows = d_rows.download(np.float64, total * 10).reshape(-1, 10)
+    return cnt, roff, d_rows.download(np.float64, total * 10).reshape(-1, 10)
+
+
+def _compose(world, Ts, Cs, dt, md):
+    """The definition: sample count -> rows -> minDistance flags -> first zero per track."""
+    nt = len(Ts)
+    cnt, roff, rows = _sample(Ts, Cs, dt)
+    total = len(rows)
     flags = world.check_states_mindist(rows[:, [0, 3, 6]], md) if total else np.zeros(0, np.uint8)
     first = np.full(nt, -1, np.int64)
     time = np.full(nt, -1.0)
@@ -186,6 +194,20 @@ def _linear(x0, vx, y, z):
     return c
 
 
+def _entry_face(ref, md):
+    """(x, y, z): where the line (y, z) along +x enters the 3-OBB world's last obstacle at md."""
+    ob = ref[2]
+    y, z = float(ob["center"][1]), 0.5
+    # by bisection on the oracle's predicate
+    lo, hi = float(ob["center"][0]) - 1.0, float(ob["center"][0])
+    probe = lambda x: O.check_states_mindist(ref, np.array([[x, y, z]]), md)[0]
+    assert probe(lo) == 1 and probe(hi) == 0
+    for _ in range(60):
+        mid = 0.5 * (lo + hi)
+        lo, hi = (mid, hi) if probe(mid) else (lo, mid)
+    return hi, y, z
+
+
 def test_chunk_and_wave_edges():
     """One-segment linear tracks x = x0 + v t flying along +x into one obstacle of the 3-OBB
     world, x0 solved on the CPU so that the first failing row is R; tracks that stay valid
@@ -193,16 +215,7 @@ def test_chunk_and_wave_edges():
     world, ref = _world(3)
     md, v = 0.05, 0.1
     step = v * DT
-    ob = ref[2]
-    y, z = float(ob["center"][1]), 0.5
-    # the entry face along the line (y, z), by bisection on the oracle's predicate
-    lo, hi = float(ob["center"][0]) - 1.0, float(ob["center"][0])
-    probe = lambda x: O.check_states_mindist(ref, np.array([[x, y, z]]), md)[0]
-    assert probe(lo) == 1 and probe(hi) == 0
-    for _ in range(60):
-        mid = 0.5 * (lo + hi)
-        lo, hi = (mid, hi) if probe(mid) else (lo, mid)
-    face = hi
+    face, y, z = _entry_face(ref, md)
     Rs = [0, 1, 63, 64, K_ROW_CHUNK - 1, K_ROW_CHUNK, K_ROW_CHUNK + 1]
     Ts, Cs, want = [], [], []
     far = _linear(face - 4.0, -v, y, z)  # flies away from the obstacle: valid
@@ -222,6 +235,40 @@ def test_chunk_and_wave_edges():
     print("edges:", got_first.tolist())
     assert np.array_equal(got_first, first)
     assert np.array_equal(got_time, time)
+
+
+def test_four_consumers_of_the_stepping_loop_agree_at_its_cap_edges():
+    """epp_sample_count, epp_sample_batch, epp_traj_check_batch and epp_traj_sweep_batch step
+    the recurrence with one loop (traj_sample.h), eight samples at once while eight more fit in
+    a chunk: one-segment linear tracks of 1, 8, 9 and kRowChunk + 1 rows flying into an obstacle
+    of the 3-OBB world beside a 30-segment fitted track, one batch.  The counts and the time
+    column are the oracle's, and a failing row's or chord's time is that column's entry."""
+    world, ref = _world(3)
+    md, v = 0.05, 0.1
+    step = v * DT
+    face, y, z = _entry_face(ref, md)
+    fit_T, fit_C = _fit("ragged")
+    n_rows = [1, 8, 9, K_ROW_CHUNK + 1]
+    # the last row half a step past the face (the 1-row track: its only row)
+    Ts = [np.array([(n - 0.5) * DT]) for n in n_rows] + [fit_T[17]]
+    Cs = [_linear(face - (n - 1) * step + 0.5 * step, v, y, z) for n in n_rows] + [fit_C[17]]
+    assert len(Ts[-1]) == 30
+    ref_rows = [O.sample_traj(T, Cf, DT) for T, Cf in zip(Ts, Cs)]
+    assert [len(r) for r in ref_rows[:4]] == n_rows
+    cnt, roff, rows = _sample(Ts, Cs, DT)
+    assert cnt.tolist() == [len(r) for r in ref_rows]
+    assert np.array_equal(rows[:, 9], np.concatenate([r[:, 9] for r in ref_rows]))
+    # (the inputs are what they are meant to be: rows and chords fail, on the oracle alone)
+    o_row = _oracle(ref, Ts, Cs, DT, md)[0]
+    o_chord = tsi.oracle_sweep(ref, Ts, Cs, DT, False)[0]
+    print("oracle rows", o_row.tolist(), "chords", o_chord.tolist())
+    assert o_row[:4].tolist() == [n - 1 for n in n_rows] and (o_chord >= 0).any()
+    for name, (first, time) in (("check", world.check_trajectories(Ts, Cs, DT, md)),
+                                ("sweep", world.sweep_trajectories(Ts, Cs, DT, False))):
+        print(name, first.tolist(), time.tolist())
+        bad = np.flatnonzero(first >= 0)
+        assert len(bad) and (first < cnt).all() and (time[first < 0] == -1.0).all()
+        assert np.array_equal(time[bad], rows[roff[bad] + first[bad], 9])
 
 
 # ---- 4. degenerate tracks -----------------------------------------------------------------

@@ -63,19 +63,27 @@ def rows_host(tmp_path_factory):
     return exe
 
 
-@pytest.mark.parametrize("dt", [0.05, 0.01, 0.1])
-def test_host_recurrence_row_count_equals_oracle(rows_host, dt):
+def _tracks(dt):
     """Ragged tracks (1..30 segments, the GPU tests' batch) and exact multiples of dt."""
     tracks = [synth.random_track_waypoints(900 + k, 1 + (k * 7) % 30) for k in range(24)]
     Ts = [O.segment_times(wp, 1.0, 2.0) for wp in tracks]
-    Ts += [np.array([0.5, 0.25, 1.0]), np.array([dt * 512]), np.array([dt * 511.5]), np.array([dt / 2])]
-    Cs = [np.zeros((len(t), 3, 10)) for t in Ts]  # (the rows' times do not depend on the coefficients)
+    return Ts + [np.array([0.5, 0.25, 1.0]), np.array([dt * 512]), np.array([dt * 511.5]), np.array([dt / 2])]
+
+
+def _run(rows_host, mode, dt, Ts):
     args = []
     for T in Ts:  # one run for all tracks
         args += (["/"] if args else []) + [repr(float(t)) for t in T]
-    run = subprocess.run([rows_host, repr(float(dt))] + args, capture_output=True, text=True)
+    run = subprocess.run([rows_host] + mode + [repr(float(dt))] + args, capture_output=True, text=True)
     assert run.returncode == 0, run.stderr
-    lines = run.stdout.splitlines()
+    return run.stdout.splitlines()
+
+
+@pytest.mark.parametrize("dt", [0.05, 0.01, 0.1])
+def test_host_recurrence_row_count_equals_oracle(rows_host, dt):
+    Ts = _tracks(dt)
+    Cs = [np.zeros((len(t), 3, 10)) for t in Ts]  # (the rows' times do not depend on the coefficients)
+    lines = _run(rows_host, [], dt, Ts)
     assert len(lines) == len(Ts)
     for T, Cf, line in zip(Ts, Cs, lines):
         out = line.split()
@@ -83,3 +91,31 @@ def test_host_recurrence_row_count_equals_oracle(rows_host, dt):
         assert int(out[0]) == len(ref), (T, out)
         if len(ref):
             assert float(out[1]) == ref[-1, 9], (T, out)
+
+
+CAPS = (1, 7, 8, 9, 512, 513)
+
+
+@pytest.mark.parametrize("dt", [0.05, 0.01, 0.1])
+def test_producer_equals_single_steps_at_every_cap(rows_host, dt):
+    """The shared stepping loop (range_produce: eight samples at once where it may, else one)
+    gives the samples of plain next / advance steps -- segment, time in the segment and time,
+    compared as printed hex floats, so bit for bit -- whatever room each call is given (below,
+    at and above the eight of the shortcut, at and above a kernel's chunk), and range_count
+    their number."""
+    Ts = _tracks(dt)
+    lines = _run(rows_host, ["samples"], dt, Ts)
+    per = 1 + len(CAPS)
+    assert len(lines) == per * len(Ts)
+    for k, T in enumerate(Ts):
+        head, _, step = lines[per * k].partition(" |")
+        way, n, counted = head.split()
+        assert way == "step" and int(n) == len(step.split()) // 3 and int(counted) == int(n), (T, head)
+        assert int(n) > 0
+        for cap, line in zip(CAPS, lines[per * k + 1:per * (k + 1)]):
+            head, _, got = line.partition(" |")
+            assert head == f"cap{cap} {n}", (T, head, n)
+            if got != step:
+                a, b = step.split(), got.split()
+                j = next(i for i in range(len(a)) if a[i] != b[i])
+                raise AssertionError((T, cap, "sample", j // 3, a[j - j % 3:j - j % 3 + 3], b[j - j % 3:j - j % 3 + 3]))

@@ -53,11 +53,15 @@ def test_symbol_wrapper_and_argument_checks():
 
 @pytest.mark.skipif(not os.path.exists(os.path.join(LLVM, "llvm-readelf")), reason="ROCm LLVM tools absent")
 def test_kernel_keeps_everything_in_registers():
-    meta = {k: v for k, v in _kernel_metadata(capi.LIB_PATH).items() if "k_traj_sweep" in k}
-    assert len(meta) == 3, sorted(meta)  # the three staging levels
-    for name, v in meta.items():
-        assert v.get("private_segment_fixed_size", 0) == 0 and v.get("vgpr_spill_count", 0) == 0, (name, v)
-        assert 0 < v["vgpr_count"] <= 128, (name, v)  # 4 waves per SIMD
+    every = _kernel_metadata(capi.LIB_PATH)
+    # k_traj_sweep: the three staging levels; k_traj_check: front staged or not
+    for kernel, variants in (("k_traj_sweep", 3), ("k_traj_check", 2)):
+        meta = {k: v for k, v in every.items() if kernel in k}
+        assert len(meta) == variants, sorted(meta)
+        for name, v in meta.items():
+            assert v.get("private_segment_fixed_size", 0) == 0 and v.get("vgpr_spill_count", 0) == 0, (name, v)
+            # 4 waves per SIMD: the 8 two-wave workgroups per CU the launcher's grid counts on
+            assert 0 < v["vgpr_count"] <= 128, (name, v)
 
 
 def test_edge_fixtures_fail_where_they_claim():
