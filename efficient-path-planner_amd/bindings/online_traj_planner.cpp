@@ -206,6 +206,56 @@ PYBIND11_MODULE(online_traj_planner, m) {
             py::arg("waypoint_sets"), py::arg("v_max"), py::arg("a_max"), py::arg("sampling_interval"),
             py::arg("min_distance"), py::arg("can_pass_gate") = false)
         .def(
+            "candidate_clearances",  // fit + closest approach of K waypoint sets (this build)
+            [](const epp::PathPlanner& self, const std::vector<py::object>& waypointSets, double vMax, double aMax,
+               double samplingInterval) {
+                std::vector<std::vector<Vec3>> sets;
+                for (const auto& o : waypointSets) {
+                    Matrix w = to_matrix(o);
+                    if (w.cols != 3) throw std::invalid_argument("waypoints must be an (n, 3) array");
+                    std::vector<Vec3> wp;
+                    for (size_t i = 0; i < w.rows; ++i) wp.emplace_back(w(i, 0), w(i, 1), w(i, 2));
+                    sets.push_back(std::move(wp));
+                }
+                std::vector<double> clearance, times;
+                std::vector<long> rows;
+                std::vector<int> nearest;
+                {
+                    py::gil_scoped_release release;
+                    self.candidateClearances(sets, vMax, aMax, samplingInterval, clearance, &rows, &times, &nearest);
+                }
+                py::array_t<double> c((py::ssize_t)clearance.size()), t((py::ssize_t)times.size());
+                py::array_t<int64_t> r((py::ssize_t)rows.size());
+                py::array_t<int32_t> o((py::ssize_t)nearest.size());
+                for (size_t i = 0; i < clearance.size(); ++i) {
+                    c.mutable_data()[i] = clearance[i];
+                    r.mutable_data()[i] = rows[i];
+                    t.mutable_data()[i] = times[i];
+                    o.mutable_data()[i] = nearest[i];
+                }
+                return py::make_tuple(c, r, t, o);
+            },
+            py::arg("waypoint_sets"), py::arg("v_max"), py::arg("a_max"), py::arg("sampling_interval"))
+        .def(
+            "clearance",  // distance to the nearest collision OBB of every point (this build)
+            [](const epp::PathPlanner& self, const py::object& points) {
+                Matrix m = to_matrix(points);
+                if (m.cols != 3) throw std::invalid_argument("points must be an (n, 3) array");
+                std::vector<double> xyz(m.rows * 3);
+                for (size_t i = 0; i < m.rows; ++i)
+                    for (size_t k = 0; k < 3; ++k) xyz[3 * i + k] = m(i, k);
+                py::array_t<double> d((py::ssize_t)m.rows);
+                py::array_t<int32_t> o((py::ssize_t)m.rows);
+                double* dp = d.mutable_data();
+                int32_t* op = o.mutable_data();
+                {
+                    py::gil_scoped_release release;
+                    self.worldPtr->clearance(xyz.data(), (int64_t)m.rows, dp, op);
+                }
+                return py::make_tuple(d, o);
+            },
+            py::arg("points"))
+        .def(
             "check_point_validity",
             [](const epp::PathPlanner& self, const py::object& p, bool canPassGate) {
                 return self.worldPtr->checkPointValidity(to_vec3(p), canPassGate);

@@ -1494,11 +1494,19 @@ namespace {
 // The fit of every waypoint set (epp_minsnap_batch) and, on the same device buffers and
 // stream, the first failing row (epp_traj_check_batch) and -- chords != nullptr -- the first
 // failing chord (epp_traj_sweep_batch) of every fitted track; one synchronisation, at the end.
-// `what` names the caller in the errors.
+// `what` names the caller in the errors.  clr != nullptr: instead of the two checks, the
+// closest approach of every fitted track's rows (epp_traj_clearance_batch) into *clr, the row
+// into firstInvalidRow and its time into rowTimes -- the same upload, fit, stream and single
+// synchronisation.
+struct CandidateClear {
+    std::vector<double>& clearance;
+    std::vector<int>* nearest;
+};
 void fit_and_check_candidates(const char* what, const epp_world* world, const std::vector<std::vector<Vec3>>& sets,
                               double v_max, double a_max, double dt, double minDistance, int32_t canPassGate,
                               std::vector<long>& firstInvalidRow, std::vector<double>* rowTimes,
-                              std::vector<long>* chords, std::vector<double>* chordTimes) {
+                              std::vector<long>* chords, std::vector<double>* chordTimes,
+                              const CandidateClear* clr = nullptr) {
     for (const auto& s : sets)
         if (s.size() < 2) throw std::invalid_argument("At least two waypoints are required");
     const size_t n = sets.size();
@@ -1506,6 +1514,10 @@ void fit_and_check_candidates(const char* what, const epp_world* world, const st
     if (rowTimes) rowTimes->assign(n, -1.0);
     if (chords) chords->assign(n, -1);
     if (chordTimes) chordTimes->assign(n, -1.0);
+    if (clr) {
+        clr->clearance.assign(n, HUGE_VAL);
+        if (clr->nearest) clr->nearest->assign(n, -1);
+    }
     if (n == 0) return;
     // host image of the upload: [waypoints | offsets]; device block: [wp | T | coeffs |
     // first_time | first_invalid | chord_time | chord | offsets | status]
@@ -1550,8 +1562,14 @@ void fit_and_check_candidates(const char* what, const epp_world* world, const st
     const int32_t* d_off = reinterpret_cast<const int32_t*>(base + o_off);
     need(epp_minsnap_batch(reinterpret_cast<const double*>(base + o_wp), d_off, (int32_t)n, v_max, a_max, nullptr,
                            nullptr, d_T, d_C, reinterpret_cast<int32_t*>(base + o_st), d.st));
-    need(epp_traj_check_batch(world, d_T, d_C, d_off, (int32_t)n, dt, minDistance,
-                              reinterpret_cast<int64_t*>(base + o_fi), reinterpret_cast<double*>(base + o_ft), d.st));
+    if (clr)  // (the chord slots hold the clearance and the nearest OBB)
+        need(epp_traj_clearance_batch(world, d_T, d_C, d_off, (int32_t)n, dt, reinterpret_cast<double*>(base + o_ct),
+                                      reinterpret_cast<int64_t*>(base + o_fi), reinterpret_cast<double*>(base + o_ft),
+                                      reinterpret_cast<int32_t*>(base + o_ci), d.st));
+    else
+        need(epp_traj_check_batch(world, d_T, d_C, d_off, (int32_t)n, dt, minDistance,
+                                  reinterpret_cast<int64_t*>(base + o_fi), reinterpret_cast<double*>(base + o_ft),
+                                  d.st));
     if (chords)
         need(epp_traj_sweep_batch(world, d_T, d_C, d_off, (int32_t)n, dt, canPassGate,
                                   reinterpret_cast<int64_t*>(base + o_ci), reinterpret_cast<double*>(base + o_ct),
@@ -1566,6 +1584,11 @@ void fit_and_check_candidates(const char* what, const epp_world* world, const st
         need(epp_memcpy_d2h_async(crows.data(), base + o_ci, n * 8, d.st));
         need(epp_memcpy_d2h_async(ctimes.data(), base + o_ct, n * 8, d.st));
     }
+    std::vector<int32_t> near(clr ? n : 0);
+    if (clr) {
+        need(epp_memcpy_d2h_async(clr->clearance.data(), base + o_ct, n * 8, d.st));
+        need(epp_memcpy_d2h_async(near.data(), base + o_ci, n * 4, d.st));
+    }
     need(epp_stream_sync(d.st));
     for (size_t k = 0; k < n; ++k)
         if (status[k] != 0)
@@ -1577,8 +1600,19 @@ void fit_and_check_candidates(const char* what, const epp_world* world, const st
     }
     if (rowTimes) *rowTimes = times;
     if (chords && chordTimes) *chordTimes = ctimes;
+    if (clr && clr->nearest) clr->nearest->assign(near.begin(), near.end());
 }
 }  // namespace
+
+void PathPlanner::candidateClearances(const std::vector<std::vector<Vec3>>& sets, double v_max, double a_max, double dt,
+                                      std::vector<double>& clearance, std::vector<long>* row,
+                                      std::vector<double>* time, std::vector<int>* nearest) const {
+    std::vector<long> rows;
+    const CandidateClear clr{clearance, nearest};
+    fit_and_check_candidates("candidateClearances", sets.empty() ? nullptr : worldPtr->device(), sets, v_max, a_max,
+                             dt, 0.0, 0, rows, time, nullptr, nullptr, &clr);
+    if (row) *row = rows;
+}
 
 bool PathPlanner::checkCandidateTrajectories(const std::vector<std::vector<Vec3>>& sets, double v_max, double a_max,
                                              double dt, double minDistance, std::vector<long>& firstInvalidRow,

@@ -1,6 +1,7 @@
 // host_world.cpp — epp::World, the drop-in for the reference's World
 // (src/World.cpp:13-162) over the device index of include/epp.h.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <stdexcept>
 #include <string>
@@ -183,16 +184,36 @@ void World::checkRaysBoth(const double* s1, const double* s2, int64_t n, uint8_t
     for (int64_t i = 0; i < n; ++i) out[i] = (uint8_t)((out[i] ? 1 : 0) | (t[i] ? 2 : 0));
 }
 
+void World::clearance(const double* xyz, int64_t n, double* dist, int32_t* nearest) const {
+    if (n <= 0) return;
+    if (!device()) {  // an empty world: nothing to be near
+        for (int64_t i = 0; i < n; ++i) {
+            dist[i] = HUGE_VAL;
+            if (nearest) nearest[i] = -1;
+        }
+        return;
+    }
+    // one output block per call: [dist (n f64) | nearest (n i32)], 12 bytes per query
+    std::vector<uint8_t> out((size_t)n * 12);
+    query(n, 1, [&](const double* const* in, uint8_t* o, void* st) {
+        check(epp_states_clearance(device(), in[0], n, reinterpret_cast<double*>(o),
+                                   reinterpret_cast<int32_t*>(o + (size_t)n * 8), st), "clearance");
+    }, [](const double* const*, uint8_t*, void*) { return false; }, &xyz, out.data(), 12);
+    std::memcpy(dist, out.data(), (size_t)n * 8);
+    if (nearest) std::memcpy(nearest, out.data() + (size_t)n * 8, (size_t)n * 4);
+}
+
 template <typename Launch, typename Small>
-void World::query(int64_t n, int n_in, Launch&& launch, Small&& small, const double* const* in, uint8_t* out) const {
+void World::query(int64_t n, int n_in, Launch&& launch, Small&& small, const double* const* in, uint8_t* out,
+                  size_t out_item) const {
     if (n <= 0) return;
     (void)device();  // upload a changed world before the launch (not inside it)
     ThreadScratch& ts = ThreadScratch::get();
     void* st = ts.stream();
-    const size_t in_b = (size_t)n * 24;
+    const size_t in_b = (size_t)n * 24, out_b = (size_t)n * out_item;
     const double* d_in[2] = {nullptr, nullptr};
     if (n <= kZeroCopyMax) {
-        char* h = static_cast<char*>(ts.pinned(0, n_in * ThreadScratch::rounded(in_b) + ThreadScratch::rounded((size_t)n)));
+        char* h = static_cast<char*>(ts.pinned(0, n_in * ThreadScratch::rounded(in_b) + ThreadScratch::rounded(out_b)));
         for (int k = 0; k < n_in; ++k) {
             std::memcpy(h + k * ThreadScratch::rounded(in_b), in[k], in_b);
             d_in[k] = reinterpret_cast<const double*>(h + k * ThreadScratch::rounded(in_b));
@@ -202,18 +223,18 @@ void World::query(int64_t n, int n_in, Launch&& launch, Small&& small, const dou
             launch(d_in, flags, st);
             check(epp_stream_sync(st), "query");
         }
-        std::memcpy(out, flags, (size_t)n);
+        std::memcpy(out, flags, out_b);
         return;
     }
-    ts.reset(n_in * ThreadScratch::rounded(in_b) + ThreadScratch::rounded((size_t)n));
+    ts.reset(n_in * ThreadScratch::rounded(in_b) + ThreadScratch::rounded(out_b));
     for (int k = 0; k < n_in; ++k) {
         double* d = static_cast<double*>(ts.carve(in_b));
         check(epp_memcpy_h2d(d, in[k], (uint64_t)in_b, st), "upload");
         d_in[k] = d;
     }
-    uint8_t* d_out = static_cast<uint8_t*>(ts.carve((size_t)n));
+    uint8_t* d_out = static_cast<uint8_t*>(ts.carve(out_b));
     launch(d_in, d_out, st);
-    check(epp_memcpy_d2h(out, d_out, (uint64_t)n, st), "download");
+    check(epp_memcpy_d2h(out, d_out, (uint64_t)out_b, st), "download");
 }
 
 bool World::checkPointValidity(const Vec3& p, bool canPassGate) const {

@@ -1,5 +1,7 @@
 // trajcheck.hip — first collision of fitted trajectories, straight from their coefficients
-// (gfx950): of their rows (k_traj_check) and of the chords between the rows (k_traj_sweep).
+// (gfx950): of their rows (k_traj_check) and of the chords between the rows (k_traj_sweep);
+// and the clearance of their rows (k_traj_clearance, below: the closest approach to a
+// collision OBB, where and against which), on the same walk.
 //
 //   PathPlanner::checkTrajectoryValidity  src/PathPlanner.cpp:267-280, per track, over the rows
 //   Trajectory::evaluateRange(0, max_time, dt)  src/trajectory.cpp:81-141 would produce, with
@@ -27,6 +29,7 @@
 #include <climits>
 #include <cmath>
 
+#include "clearance.h"
 #include "collision_common.h"
 #include "traj_sample.h"
 
@@ -92,6 +95,9 @@ __device__ __forceinline__ Acc tc_stage(const WorldView& w, unsigned char* lds, 
 //   keep(s, b)                      thread 0, before it overwrites half b ^ 1
 //   check(s, b, cnt, base, lane, coeffs, seg0)   wave 1: atomicMin(&s.first[b], j) for a failing j
 //   row(f), time(s, b, f)           the answer for posted sample f of half b, relative to base
+//   end(t, tid, walked, res, rtime, first_invalid, first_time)   the track is over (every thread;
+//                                   walked: it had a segment): write its outputs.  A check that
+//                                   never posts walks every chunk and answers from its own state.
 template <class Check>
 __device__ __forceinline__ void tc_walk(TcShared& s, const double* __restrict__ seg_times,
                                         const double* __restrict__ coeffs, const int32_t* __restrict__ wp_off,
@@ -155,15 +161,23 @@ __device__ __forceinline__ void tc_walk(TcShared& s, const double* __restrict__ 
                 b ^= 1;
             }
         }
+        chk.end(t, tid, M >= 1, res, rtime, first_invalid, first_time);
+    }
+}
+
+// How the two first-failure checks end a track: thread 0 writes the walk's answer.
+struct TcFirst {
+    __device__ __forceinline__ void end(int t, int tid, bool, int64_t res, double rtime,
+                                        int64_t* __restrict__ first_invalid, double* __restrict__ first_time) {
         if (tid == 0) {
             first_invalid[t] = res;
             if (first_time) first_time[t] = rtime;
         }
     }
-}
+};
 
 // The rows: World::checkPointValidity(p_j, minDistance).  A lane takes samples lane, + 64, ...
-struct TcPoints {
+struct TcPoints : TcFirst {
     const Acc& a;
     const WorldView& w;
     double md;
@@ -200,7 +214,7 @@ struct TcPoints {
 // LDS result word of a half: the lowest failing chord's END sample in the half (0: the chord
 // from the previous chunk); its time is the START row's, which for 0 lies in the half the
 // producer is overwriting: thread 0 keeps it (prev_tac) before it produces.
-struct TcChords {
+struct TcChords : TcFirst {
     const Acc& a;
     const WorldView& w;
     bool cp;
@@ -249,6 +263,92 @@ struct TcChords {
     }
 };
 
+// The clearance of the rows: the minimum over a track's rows of the squared distance to the
+// nearest collision OBB (clearance.h), where it is attained and against which OBB.  Nothing is
+// ever posted to first[], so the walk visits every chunk of every track.  A checking lane
+// takes samples lane, + 64, ... and keeps its best (d2, row, time, OBB) in registers across
+// the chunks, updating on strict <: its rows ascend, so the earliest row wins within a lane,
+// and within a row the lowest OBB index (clear_min_*).  At the track's end wave 1 reduces
+// lexicographically by (d2, row).  A row with a non-finite position has a NaN or +inf d2 and
+// never updates.  The first n_lds entries come from the LDS tile staged behind TcShared, the
+// rest of a larger world from its records through L2.
+struct TcClearOut {
+    double* clearance;
+    int32_t* nearest;
+};
+struct TcClear {
+    const double* tile;   // LDS: entries [0, n_lds)
+    const double* recs;   // the world's records
+    int n_lds, n_obb;
+    TcClearOut out;
+    double bd2, btime;    // wave 1: the lane's best so far
+    int64_t brow;
+    int bobb;
+    __device__ __forceinline__ void reset() {
+        bd2 = HUGE_VAL;
+        brow = -1;
+        btime = -1.0;
+        bobb = -1;
+    }
+    __device__ __forceinline__ void begin() { reset(); }
+    __device__ __forceinline__ void keep(const TcShared&, int) {}
+    __device__ __forceinline__ void check(TcShared& s, int b, int cnt, int64_t base, int lane,
+                                          const double* __restrict__ coeffs, int seg0) {
+        for (int j = lane; j < cnt; j += kTcCheckers) {
+            double p[3];
+            tc_pos(s, b, j, coeffs, seg0, p);
+            double d2 = HUGE_VAL;
+            int o = -1;
+            clear_min_tile(tile, 0, n_lds, p[0], p[1], p[2], d2, o);
+            clear_min_recs(recs, n_lds, n_obb, p[0], p[1], p[2], d2, o);
+            const bool lt = d2 < bd2;
+            bd2 = lt ? d2 : bd2;
+            brow = lt ? base + j : brow;
+            btime = lt ? s.tac[b][j] : btime;
+            bobb = lt ? o : bobb;
+        }
+    }
+    __device__ __forceinline__ int row(int f) const { return f; }                           // (never posted:
+    __device__ __forceinline__ double time(const TcShared&, int, int) const { return 0.0; }  //  never asked)
+    __device__ __forceinline__ void end(int t, int tid, bool walked, int64_t, double, int64_t* __restrict__ row_out,
+                                        double* __restrict__ time_out) {
+        if (tid < 64) return;  // (wave-uniform: wave 1 holds the bests)
+        if (!walked) reset();  // no segment, no row
+        for (int m = 32; m > 0; m >>= 1) {
+            const double od2 = __shfl_xor(bd2, m), otime = __shfl_xor(btime, m);
+            const long long orow = __shfl_xor((long long)brow, m);
+            const int oobb = __shfl_xor(bobb, m);
+            const bool take = od2 < bd2 || (od2 == bd2 && orow < brow);
+            bd2 = take ? od2 : bd2;
+            brow = take ? orow : brow;
+            btime = take ? otime : btime;
+            bobb = take ? oobb : bobb;
+        }
+        if (tid == 64) {
+            out.clearance[t] = sqrt(bd2);  // once, after the minimum
+            if (row_out) row_out[t] = brow;
+            if (time_out) time_out[t] = btime + 0.0;  // epp_sample_batch's time column with t0 == NULL
+            if (out.nearest) out.nearest[t] = bobb;
+        }
+    }
+};
+
+__global__ __launch_bounds__(kTcBlock) void k_traj_clearance(WorldView w, const double* __restrict__ seg_times,
+                                                             const double* __restrict__ coeffs,
+                                                             const int32_t* __restrict__ wp_off, int n_tracks,
+                                                             double dt, TcClearOut out, int64_t* __restrict__ row,
+                                                             double* __restrict__ time, uint32_t stage_bytes) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    double* tile = reinterpret_cast<double*>(lds + kTcSharedBytes);
+    const double* recs = reinterpret_cast<const double*>(w.blob + w.off_aos);
+    const int n_lds = (int)(stage_bytes / (kClearDoubles * sizeof(double)));
+    clear_stage(recs, 0, n_lds, tile, kTcBlock);
+    __syncthreads();
+    TcClear chk{tile, recs, n_lds, w.n_obb, out};
+    chk.reset();
+    tc_walk(*reinterpret_cast<TcShared*>(lds), seg_times, coeffs, wp_off, n_tracks, dt, row, time, chk);
+}
+
 template <bool STAGE>
 __global__ __launch_bounds__(kTcBlock) void k_traj_check(WorldView w, const double* __restrict__ seg_times,
                                                          const double* __restrict__ coeffs,
@@ -258,7 +358,7 @@ __global__ __launch_bounds__(kTcBlock) void k_traj_check(WorldView w, const doub
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const Acc a = tc_stage<STAGE ? 1 : 0>(w, lds, stage_bytes);
     tc_walk(*reinterpret_cast<TcShared*>(lds), seg_times, coeffs, wp_off, n_tracks, dt, first_invalid, first_time,
-            TcPoints{a, w, md});
+            TcPoints{{}, a, w, md});
 }
 
 template <int STAGE>
@@ -270,11 +370,11 @@ __global__ __launch_bounds__(kTcBlock) void k_traj_sweep(WorldView w, const doub
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const Acc a = tc_stage<STAGE>(w, lds, stage_bytes);
     tc_walk(*reinterpret_cast<TcShared*>(lds), seg_times, coeffs, wp_off, n_tracks, dt, first_invalid, first_time,
-            TcChords{a, w, can_pass != 0});
+            TcChords{{}, a, w, can_pass != 0});
 }
 
 // What both entry points do around their kernels.  P: the check's own parameter (kernel
-// argument 7); ok: the entry point's own argument checks; kernels: its kernel per staging
+// argument 7); ok: the entry point's own argument checks (its required output among them); kernels: its kernel per staging
 // level; stage(view, bytes): the level for this world, and how many bytes it stages.
 template <class P>
 using TcKernel = void (*)(WorldView, const double*, const double*, const int32_t*, int, double, P, int64_t*, double*,
@@ -285,7 +385,7 @@ epp_status tc_launch(const char* fn, bool ok, const TcKernel<P>* kernels, Stage 
                      const double* seg_times, const double* coeffs, const int32_t* wp_offsets, int32_t n_tracks,
                      double dt, P param, int64_t* first_invalid, double* first_time, void* stream) {
     if (!ok || !world || n_tracks < 0 || !(dt > 0) || !std::isfinite(dt) ||
-        (n_tracks > 0 && (!seg_times || !coeffs || !wp_offsets || !first_invalid))) {
+        (n_tracks > 0 && (!seg_times || !coeffs || !wp_offsets))) {
         set_error(std::string(fn) + ": invalid argument");
         return EPP_ERR_INVALID_ARGUMENT;
     }
@@ -323,7 +423,7 @@ epp_status epp_traj_check_batch(const epp_world* world, const double* seg_times,
         bytes = v.front_bytes;
         return 1;
     };
-    return tc_launch("epp_traj_check_batch", true, kernels, stage, world, seg_times, coeffs, wp_offsets, n_tracks, dt,
+    return tc_launch("epp_traj_check_batch", n_tracks <= 0 || first_invalid, kernels, stage, world, seg_times, coeffs, wp_offsets, n_tracks, dt,
                      min_distance, first_invalid, first_time, stream);
 }
 
@@ -346,9 +446,25 @@ epp_status epp_traj_sweep_batch(const epp_world* world, const double* seg_times,
         }
         return 0;
     };
-    return tc_launch("epp_traj_sweep_batch", can_pass_gate == 0 || can_pass_gate == 1, kernels, stage, world,
+    return tc_launch("epp_traj_sweep_batch", (can_pass_gate == 0 || can_pass_gate == 1) && (n_tracks <= 0 || first_invalid),
+                     kernels, stage, world,
                      seg_times, coeffs, wp_offsets, n_tracks, dt, (int)can_pass_gate, first_invalid, first_time,
                      stream);
+}
+
+epp_status epp_traj_clearance_batch(const epp_world* world, const double* seg_times, const double* coeffs,
+                                    const int32_t* wp_offsets, int32_t n_tracks, double dt, double* clearance,
+                                    int64_t* row, double* time, int32_t* nearest, void* stream) {
+    static constexpr TcKernel<TcClearOut> kernels[] = {k_traj_clearance};
+    // The first tile of entries in LDS; a larger world's remaining records are read through
+    // L2.  EPP_TRAJCLEAR_STAGE=0: every record through L2 (A/B and test knob)
+    const auto stage = [](const WorldView& v, uint32_t& bytes) {
+        if (env_int("EPP_TRAJCLEAR_STAGE", 1) != 0)
+            bytes = (uint32_t)std::min(v.n_obb, kClearTile) * (uint32_t)(kClearDoubles * sizeof(double));
+        return 0;
+    };
+    return tc_launch("epp_traj_clearance_batch", n_tracks <= 0 || clearance, kernels, stage, world, seg_times, coeffs,
+                     wp_offsets, n_tracks, dt, TcClearOut{clearance, nearest}, row, time, stream);
 }
 
 }  // extern "C"

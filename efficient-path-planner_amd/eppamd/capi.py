@@ -97,6 +97,8 @@ def lib() -> C.CDLL:
             "epp_traj_scale_to_limits": (i32, [vp, vp, vp, i32, dp, dp, vp, vp, vp]),
             "epp_traj_check_batch": (i32, [vp, vp, vp, vp, i32, dp, dp, vp, vp, vp]),
             "epp_traj_sweep_batch": (i32, [vp, vp, vp, vp, i32, dp, i32, vp, vp, vp]),
+            "epp_states_clearance": (i32, [vp, vp, i64, vp, vp, vp]),
+            "epp_traj_clearance_batch": (i32, [vp, vp, vp, vp, i32, dp, vp, vp, vp, vp, vp]),
             "epp_generate_trajectory_limited_host": (i32, [vp, i32, dp, dp, dp, dp, vp, vp,
                                                            C.POINTER(C.POINTER(C.c_double)), C.POINTER(i64),
                                                            C.POINTER(C.c_double)]),
@@ -156,7 +158,7 @@ EXPORTED = [
     "epp_comm_allreduce_f64", "epp_comm_barrier", "epp_comm_available", "epp_knn_ws_box", "epp_knn_grid_ws_box",
     "epp_comm_set_timeout", "epp_comm_abort", "epp_check_and_generate_trajectory_host",
     "epp_traj_peaks", "epp_traj_scale_to_limits", "epp_generate_trajectory_limited_host",
-    "epp_traj_check_batch", "epp_traj_sweep_batch",
+    "epp_traj_check_batch", "epp_traj_sweep_batch", "epp_states_clearance", "epp_traj_clearance_batch",
 ]
 
 
@@ -345,6 +347,35 @@ class World:
                                          1 if can_pass_gate else 0, d_row.ptr, d_time.ptr, None))
         sync()
         return d_row.download(np.int64, nt), d_time.download(np.float64, nt)
+
+    def clearance(self, points: np.ndarray):
+        """epp_states_clearance: per point the Euclidean distance to the nearest collision
+        (non-filling) OBB, 0 inside or on one, and that OBB's index in the world's order (the
+        lowest index among equals); (+inf, -1) without a collision OBB or for a non-finite
+        point.  Returns (float64[n], int32[n])."""
+        xyz = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+        n = len(xyz)
+        d_xyz = DeviceBuffer.from_array(xyz)
+        d_dist, d_near = DeviceBuffer(8 * n), DeviceBuffer(4 * n)
+        check(lib().epp_states_clearance(self.handle, d_xyz.ptr, n, d_dist.ptr, d_near.ptr, None))
+        sync()
+        return d_dist.download(np.float64, n), d_near.download(np.int32, n)
+
+    def trajectory_clearance(self, Ts, Cs, dt: float):
+        """epp_traj_clearance_batch on the lists minsnap_batch returns: per track the closest
+        approach of its sampled rows (Trajectory::evaluateRange at dt) to a collision OBB, the
+        earliest row that attains it, that row's time and its nearest OBB; (+inf, -1, -1.0, -1)
+        for a track without rows or a world without collision OBBs.  Returns (float64[n],
+        int64[n], float64[n], int32[n])."""
+        nt = len(Ts)
+        d_T, d_C, d_off, _, _ = _upload_tracks(Ts, Cs)
+        d_clr, d_row, d_time, d_near = (DeviceBuffer(8 * nt), DeviceBuffer(8 * nt), DeviceBuffer(8 * nt),
+                                        DeviceBuffer(4 * nt))
+        check(lib().epp_traj_clearance_batch(self.handle, d_T.ptr, d_C.ptr, d_off.ptr, nt, float(dt), d_clr.ptr,
+                                             d_row.ptr, d_time.ptr, d_near.ptr, None))
+        sync()
+        return (d_clr.download(np.float64, nt), d_row.download(np.int64, nt), d_time.download(np.float64, nt),
+                d_near.download(np.int32, nt))
 
 
 def minsnap_batch(tracks, v_max, a_max, v0=None, a0=None):

@@ -35,6 +35,9 @@
  *   epp_traj_sweep_batch
  *       World::checkRayValid (src/World.cpp:130-162) on the chords between consecutive rows
  *       of every fitted track: the first failing chord per track.
+ *   epp_states_clearance / epp_traj_clearance_batch
+ *       no reference counterpart: the Euclidean distance to the nearest collision OBB, per
+ *       state and as the closest approach of every fitted track's rows.
  */
 #ifndef EPP_H_
 #define EPP_H_
@@ -260,6 +263,50 @@ epp_status epp_traj_check_batch(const epp_world* w, const double* seg_times, con
 epp_status epp_traj_sweep_batch(const epp_world* w, const double* seg_times, const double* coeffs,
                                 const int32_t* wp_offsets, int32_t n_tracks, double dt, int32_t can_pass_gate,
                                 int64_t* first_invalid, double* first_time, void* stream);
+
+/* ---- clearance: the Euclidean distance to the nearest collision OBB (device pointers) ---
+ * For a point p and OBB i with filling == 0 (filling OBBs are skipped, as the minDistance
+ * check skips them), every operation one IEEE fp64 multiply, add or subtract in this
+ * association:
+ *   dx = px - cx;  dy = py - cy;  dz = pz - cz
+ *   lx = c*dx + s*dy;  ly = c*dy - s*dx              (c, s: the cos / sin of the OBB's yaw)
+ *   ex = max(|lx| - hx, 0);  ey = max(|ly| - hy, 0);  ez = max(|dz| - hz, 0)   (not inflated)
+ *   d2_i = (ex*ex + ey*ey) + ez*ez
+ * d2(p) = min_i d2_i; the nearest OBB is the lowest index i, in the order given to
+ * epp_world_create / epp_world_update, that attains it.  The distance is sqrt(d2), taken once
+ * after the minimum: 0 inside or on a box.  No grid, no AABB prefilter and no inflate radius
+ * take part, so a point far from everything has its exact distance.  A world without
+ * collision OBBs gives +inf and OBB -1; a NaN d2_i never updates the minimum, so a
+ * non-finite point gives +inf / -1 too.
+ *
+ * epp_states_clearance: dist[i] (n, device f64) and nearest[i] (n, device int32, may be
+ * NULL) for each of the n states xyz (n x 3 f64).  Stream-ordered, no host synchronisation
+ * and no allocation; a stale world index is rebuilt first, as by epp_check_states_mindist,
+ * so the call can be captured (epp_graph_begin) after epp_world_build_index.
+ * EPP_ERR_INVALID_ARGUMENT (before any device work) for a NULL world, n < 0, or a NULL xyz
+ * or dist with n > 0; n == 0 launches nothing. */
+epp_status epp_states_clearance(const epp_world* w, const double* xyz, int64_t n, double* dist, int32_t* nearest,
+                                void* stream);
+/* The closest approach of every track of a batch in the layout of epp_minsnap_batch, straight
+ * from the coefficients, in one launch and without writing a row.  Over the positions of the
+ * rows of Trajectory::evaluateRange(0, max_time, dt) of track k: clearance[k] (n_tracks,
+ * device f64) is the square root of the minimum d2; row[k] (device int64, may be NULL) the
+ * earliest row that attains it; time[k] (device f64, may be NULL) that row's time column as
+ * epp_sample_batch writes it with t0 == NULL; nearest[k] (device int32, may be NULL) the
+ * nearest OBB of that row.  A track without rows (one waypoint, the NaN times of a failed
+ * fit) or a world without collision OBBs gives +inf, -1, -1.0, -1; rows with a non-finite
+ * position are ignored.  The answers are those of epp_sample_count + epp_sample_batch +
+ * epp_states_clearance on the rows' columns 0 / 3 / 6 followed by a per-track minimum that
+ * prefers the earliest row, bit for bit (the same recurrence, Horner steps and d2, one
+ * square root after an exact minimum).  Stream-ordered, no host synchronisation and no
+ * allocation; a stale world index is rebuilt first, as by epp_check_states_mindist, so the
+ * call can be captured (epp_graph_begin) after epp_world_build_index.
+ * EPP_ERR_INVALID_ARGUMENT (before any device work) for a NULL world, n_tracks < 0, dt <= 0
+ * or not finite, or a NULL seg_times, coeffs, wp_offsets or clearance with n_tracks > 0;
+ * n_tracks == 0 launches nothing. */
+epp_status epp_traj_clearance_batch(const epp_world* w, const double* seg_times, const double* coeffs,
+                                    const int32_t* wp_offsets, int32_t n_tracks, double dt, double* clearance,
+                                    int64_t* row, double* time, int32_t* nearest, void* stream);
 
 /* ---- batch planner building blocks (device pointers) ------------------------------- */
 /* Replace OMPL's sampler / nearest-neighbour structure behind PathPlanner::planPath

@@ -132,6 +132,17 @@ public:
                                     double dt, double minDistance, bool canPassGate,
                                     std::vector<long>& firstInvalidRow, std::vector<long>& firstInvalidChord,
                                     std::vector<double>* firstInvalidTime = nullptr) const;
+    // How close each of K candidate waypoint sets' trajectories comes to an obstacle (an
+    // addition of this build), to rank valid candidates: the fit of every set as above and, on
+    // the same stream with one synchronisation, epp_traj_clearance_batch (include/epp.h) of
+    // the fits' rows at dt.  clearance[k]: the smallest Euclidean distance from a row of set k
+    // to a collision (non-filling) OBB, 0 for a row inside one, +inf for a world without any;
+    // row / time / nearest (optional): the earliest row that attains it, its time, and the
+    // nearest OBB's index in the world's order (the lowest among equals); -1, -1.0, -1 when
+    // the clearance is +inf.  Throws as checkCandidateTrajectories.
+    void candidateClearances(const std::vector<std::vector<Vec3>>& waypointSets, double v_max, double a_max, double dt,
+                             std::vector<double>& clearance, std::vector<long>* row = nullptr,
+                             std::vector<double>* time = nullptr, std::vector<int>* nearest = nullptr) const;
     std::vector<Vec3> includeGates2(std::vector<std::vector<Vec3>> waypoints) const;
     // planPaths of consecutive gate-to-gate segments, then includeGates2 of their paths (an
     // addition of this build, for OnlineTrajGenerator::preComputeTraj): the same answers as

@@ -51,6 +51,11 @@ public:
     // with canPassGate = false, bit 1 = valid with true.  One launch when the batch takes the
     // small path (k_motions_small tests each ray once for both), else two.
     void checkRaysBoth(const double* s1, const double* s2, int64_t n, uint8_t* out) const;
+    // Clearance (an addition of this build; epp_states_clearance, include/epp.h): dist[i] is the
+    // Euclidean distance from point i to the nearest collision (non-filling) OBB, 0 inside or
+    // on one; nearest[i] (optional) that OBB's index in obbs(), the lowest among equals.
+    // +inf / -1 without a collision OBB (an empty world included) or for a non-finite point.
+    void clearance(const double* xyz, int64_t n, double* dist, int32_t* nearest = nullptr) const;
 
     // Device handle (rebuilt lazily after mutations); nullptr for an empty world.
     const epp_world* device() const;
@@ -68,7 +73,8 @@ private:
     void addObject(int id, bool gate, const std::vector<double>& coordinates, bool update);
     void sync() const;
     template <typename Launch, typename Small>
-    void query(int64_t n, int n_in, Launch&& launch, Small&& small, const double* const* in, uint8_t* out) const;
+    void query(int64_t n, int n_in, Launch&& launch, Small&& small, const double* const* in, uint8_t* out,
+               size_t out_item = 1) const;  // out_item: output bytes per query
 
     std::shared_ptr<ConfigParser> config_;
     double rGate_, rObst_;

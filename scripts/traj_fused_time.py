@@ -10,6 +10,11 @@ against the 72-OBB world (synth.track_world(42), configs/config_filling.json).  
             World::checkRayValid, can_pass_gate 0) against epp_sample_count + epp_sample_batch +
             epp_check_motions (mode 0) on the two contiguous n x 3 edge arrays of consecutive
             positions
+    clearance  epp_traj_clearance_batch (closest approach of the rows to a collision OBB)
+            against epp_sample_count + epp_sample_batch + epp_states_clearance on the n x 3
+            repack; nothing exits early here, so "valid" (10 m above everything) and "mixed"
+            do the same work.  --obbs 300 runs the 300-OBB world (synth.track_world(7, 8, 252)):
+            more than one LDS tile of records
 
 The fused call is one launch and writes no row; the repack of the composed one, a host step
 today, is made once outside the timing.  Two cases: "valid" (every track lifted 10 m, above
@@ -22,6 +27,7 @@ of the two sampling calls reads the track offsets back inside its pair, as it al
 
     python scripts/traj_fused_time.py --kind point [--reps 20] [--out profiles/traj_check_time.json]
     python scripts/traj_fused_time.py --kind chord [--reps 20] [--out profiles/traj_sweep_time.json]
+    python scripts/traj_fused_time.py --kind clearance [--obbs 300] [--out profiles/traj_clearance_time.json]
 """
 import argparse
 import ctypes as C
@@ -39,7 +45,8 @@ from eppamd import capi, config, synth  # noqa: E402
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--kind", choices=("point", "chord"), required=True)
+    ap.add_argument("--kind", choices=("point", "chord", "clearance"), required=True)
+    ap.add_argument("--obbs", type=int, choices=(72, 300), default=72)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--tracks", type=int, default=4096)
@@ -49,11 +56,14 @@ def main():
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     L = capi.lib()
-    point = a.kind == "point"
+    clear = a.kind == "clearance"
+    point = a.kind == "point" or clear  # (the items are the rows)
     nt, dt, md, cp = a.tracks, a.dt, a.min_distance, a.can_pass_gate
     cfg = config.load(os.path.join(ROOT, "configs", "config_filling.json"))
     rg, ro = config.inflate_radii(cfg)
-    world = capi.World(capi.build_obbs(config.geometry(cfg), *synth.track_world(42)), rg, ro)
+    poses = synth.track_world(42) if a.obbs == 72 else synth.track_world(7, n_gates=8, n_obstacles=252)
+    world = capi.World(capi.build_obbs(config.geometry(cfg), *poses), rg, ro)
+    assert world.n == a.obbs
     world.build_index()
     stream = C.c_void_p()
     capi.check(L.epp_stream_create(C.byref(stream)))
@@ -65,6 +75,7 @@ def main():
     d_T, d_C = capi.DeviceBuffer(8 * 12 * nt), capi.DeviceBuffer(240 * 12 * nt)
     d_st, d_cnt, d_roff = capi.DeviceBuffer(4 * nt), capi.DeviceBuffer(8 * nt), capi.DeviceBuffer(8 * nt)
     d_first, d_time = capi.DeviceBuffer(8 * nt), capi.DeviceBuffer(8 * nt)
+    d_clr, d_near = capi.DeviceBuffer(8 * nt), capi.DeviceBuffer(4 * nt)  # (clearance)
 
     def timed(fn):
         ms = []
@@ -80,7 +91,8 @@ def main():
         ms = np.array(ms)
         return {"median_ms": float(np.median(ms)), "min_ms": float(ms.min()), "max_ms": float(ms.max())}
 
-    res = {"tracks": nt, "segments": 12, "dt": dt, **({"min_distance": md} if point else {"can_pass_gate": cp}),
+    res = {"tracks": nt, "segments": 12, "dt": dt,
+           **({} if clear else {"min_distance": md} if point else {"can_pass_gate": cp}),
            "obbs": world.n, "reps": a.reps, "warmup": a.warmup}
     for case, lift in (("valid", 10.0), ("mixed", 0.0)):
         tracks = [synth.random_track_waypoints(10_000 + k, 12) + [0.0, 0.0, lift] for k in range(nt)]
@@ -121,23 +133,29 @@ def main():
             ioff[1:] = np.cumsum(per_track)
             d_in = [capi.DeviceBuffer.from_array(np.ascontiguousarray(xyz[si + k]), stream) for k in (0, 1)]
         d_valid = capi.DeviceBuffer(n_items)
+        d_dist, d_nr = capi.DeviceBuffer(8 * n_items if clear else 16), capi.DeviceBuffer(4 * n_items if clear else 16)
 
         def composed_check():
-            if point:
+            if clear:
+                capi.check(L.epp_states_clearance(world.handle, d_in[0].ptr, n_items, d_dist.ptr, d_nr.ptr, stream))
+            elif point:
                 capi.check(L.epp_check_states_mindist(world.handle, d_in[0].ptr, n_items, md, d_valid.ptr, stream))
             else:
                 capi.check(L.epp_check_motions(world.handle, d_in[0].ptr, d_in[1].ptr, n_items, cp, 0, d_valid.ptr,
                                                stream))
 
         def fused():
-            if point:
+            if clear:
+                capi.check(L.epp_traj_clearance_batch(world.handle, d_T.ptr, d_C.ptr, d_off.ptr, nt, dt, d_clr.ptr,
+                                                      d_first.ptr, d_time.ptr, d_near.ptr, stream))
+            elif point:
                 capi.check(L.epp_traj_check_batch(world.handle, d_T.ptr, d_C.ptr, d_off.ptr, nt, dt, md, d_first.ptr,
                                                   d_time.ptr, stream))
             else:
                 capi.check(L.epp_traj_sweep_batch(world.handle, d_T.ptr, d_C.ptr, d_off.ptr, nt, dt, cp, d_first.ptr,
                                                   d_time.ptr, stream))
 
-        check_key = "check_states_mindist" if point else "check_motions"
+        check_key = "states_clearance" if clear else "check_states_mindist" if point else "check_motions"
         r = {"rows": n_rows} if point else {"rows": n_rows, "chords": n_items}
         print(f"{case}: {n_rows} rows, {n_items} items uploaded; timing", file=sys.stderr, flush=True)
         r["fused"] = timed(fused)
@@ -148,6 +166,17 @@ def main():
         r["composed"] = {k: float(sum(r[p][k] for p in parts)) for k in ("median_ms", "min_ms", "max_ms")}
         r["composed_over_fused"] = r["composed"]["median_ms"] / r["fused"]["median_ms"]
         # the same answers, or the times compare different work
+        if clear:
+            dist = d_dist.download(np.float64, n_items, stream)
+            exp_clr = np.array([dist[roff[k]:roff[k + 1]].min() if cnt[k] else np.inf for k in range(nt)])
+            got_clr = d_clr.download(np.float64, nt, stream)
+            assert np.array_equal(got_clr, exp_clr), "fused and composed answers differ"
+            r["clearance_min"], r["clearance_max"] = float(got_clr.min()), float(got_clr.max())
+            r["tracks_touching"] = int((got_clr == 0).sum())
+            res[case] = r
+            for b in (d_rows, d_valid, d_wp, d_dist, d_nr, *d_in):
+                b.free()
+            continue
         first = d_first.download(np.int64, nt, stream)
         flags = d_valid.download(np.uint8, n_items, stream)
         exp = np.full(nt, -1, np.int64)
