@@ -1,0 +1,244 @@
+// host_candidates.cpp — epp::PathPlanner's checks of trajectories against the world: a
+// sampled trajectory's rows (checkTrajectoryValidity*) and candidate waypoint sets, fitted
+// and checked on the device in one batch (the three *Candidate* calls).
+#include <algorithm>
+#include <cmath>
+#include <stdexcept>
+#include <string>
+
+#include "epp/PathPlanner.h"
+#include "epp/trajectory_generator.h"
+#include "epp_internal.h"
+
+namespace epp {
+
+namespace {
+// The positions (columns 0, 3, 6) of a trajectory's rows as x, y, z.
+void traj_xyz(const Matrix& traj, std::vector<double>& xyz) {
+    xyz.resize(traj.rows * 3);
+    for (size_t i = 0; i < traj.rows; ++i) {
+        xyz[3 * i] = traj(i, 0);
+        xyz[3 * i + 1] = traj(i, 3);
+        xyz[3 * i + 2] = traj(i, 6);
+    }
+}
+bool all_set(const std::vector<uint8_t>& ok) {
+    return std::find(ok.begin(), ok.end(), uint8_t(0)) == ok.end();
+}
+}  // namespace
+
+// PathPlanner::checkTrajectoryValidity — src/PathPlanner.cpp:267-280 (one batched launch)
+bool PathPlanner::checkTrajectoryValidity(const Matrix& traj, double minDistance) const {
+    return checkTrajectoryValidityOn(*worldPtr, traj, minDistance);
+}
+
+bool PathPlanner::checkTrajectoryValidityOn(const World& world, const Matrix& traj, double minDistance) {
+    if (traj.rows == 0) return true;
+    std::vector<double> xyz;
+    traj_xyz(traj, xyz);
+    std::vector<uint8_t> ok(traj.rows);
+    world.checkPointsMinDistance(xyz.data(), (int64_t)traj.rows, minDistance, ok.data());
+    return all_set(ok);
+}
+
+bool PathPlanner::checkTrajectoryValidityAndGenerate(const Matrix& traj, double minDistance,
+                                                     const std::vector<Vec3>& waypoints, double vMax, double aMax,
+                                                     double samplingInterval, double startTimeOffset, const Vec3& v0,
+                                                     const Vec3& a0, Matrix& result) const {
+    if (waypoints.size() < 2) throw std::invalid_argument("At least two waypoints are required");
+    thread_local std::vector<double> xyz, wp;
+    thread_local std::vector<uint8_t> ok;
+    traj_xyz(traj, xyz);
+    wp.resize(waypoints.size() * 3);
+    for (size_t i = 0; i < waypoints.size(); ++i) {
+        wp[3 * i] = waypoints[i].x;
+        wp[3 * i + 1] = waypoints[i].y;
+        wp[3 * i + 2] = waypoints[i].z;
+    }
+    ok.assign(traj.rows, 0);
+    const double v[3] = {v0.x, v0.y, v0.z}, a[3] = {a0.x, a0.y, a0.z};
+    const FusedCheck chk{worldPtr->device(), xyz.data(), (int64_t)traj.rows, minDistance, ok.data()};
+    Matrix tmp;
+    std::swap(tmp, result);  // (result keeps its old value if the call throws)
+    auto into = [](void* ctx, int64_t R) -> double* {
+        Matrix& m = *static_cast<Matrix*>(ctx);
+        m.rows = (size_t)R;
+        m.cols = 10;
+        m.data.resize((size_t)std::max<int64_t>(R, 1) * 10);
+        return m.data.data();
+    };
+    int64_t n = 0;
+    const epp_status rc = check_and_generate_into(traj.rows ? &chk : nullptr, wp.data(), (int32_t)waypoints.size(),
+                                                  nullptr, vMax, aMax, samplingInterval, startTimeOffset, v, a, into,
+                                                  &tmp, &n);
+    if (rc == EPP_ERR_UNSUPPORTED) {  // (a large check: the two calls)
+        std::swap(tmp, result);
+        const bool valid = checkTrajectoryValidity(traj, minDistance);
+        poly_traj::generateTrajectory(waypoints, vMax, aMax, samplingInterval, startTimeOffset, v0, a0, result);
+        return valid;
+    }
+    if (rc != EPP_OK) {
+        std::swap(tmp, result);
+        if (rc == EPP_ERR_INVALID_ARGUMENT) throw std::invalid_argument(epp_last_error());
+        throw std::runtime_error(std::string("generateTrajectory: ") + epp_last_error());
+    }
+    tmp.data.resize((size_t)n * 10);
+    std::swap(tmp, result);
+    return all_set(ok);
+}
+
+namespace {
+// The fit of every waypoint set (epp_minsnap_batch) and, on the same device buffers and
+// stream, the first failing row (epp_traj_check_batch) and -- chords != nullptr -- the first
+// failing chord (epp_traj_sweep_batch) of every fitted track; one synchronisation, at the end.
+// `what` names the caller in the errors.  clr != nullptr: instead of the two checks, the
+// closest approach of every fitted track's rows (epp_traj_clearance_batch) into *clr, the row
+// into firstInvalidRow and its time into rowTimes -- the same upload, fit, stream and single
+// synchronisation.
+struct CandidateClear {
+    std::vector<double>& clearance;
+    std::vector<int>* nearest;
+};
+void fit_and_check_candidates(const char* what, const epp_world* world, const std::vector<std::vector<Vec3>>& sets,
+                              double v_max, double a_max, double dt, double minDistance, int32_t canPassGate,
+                              std::vector<long>& firstInvalidRow, std::vector<double>* rowTimes,
+                              std::vector<long>* chords, std::vector<double>* chordTimes,
+                              const CandidateClear* clr = nullptr) {
+    for (const auto& s : sets)
+        if (s.size() < 2) throw std::invalid_argument("At least two waypoints are required");
+    const size_t n = sets.size();
+    firstInvalidRow.assign(n, -1);
+    if (rowTimes) rowTimes->assign(n, -1.0);
+    if (chords) chords->assign(n, -1);
+    if (chordTimes) chordTimes->assign(n, -1.0);
+    if (clr) {
+        clr->clearance.assign(n, HUGE_VAL);
+        if (clr->nearest) clr->nearest->assign(n, -1);
+    }
+    if (n == 0) return;
+    // host image of the upload: [waypoints | offsets]; device block: [wp | T | coeffs |
+    // first_time | first_invalid | chord_time | chord | offsets | status]
+    size_t total = 0;
+    for (const auto& s : sets) total += s.size();
+    const size_t nseg = total - n;
+    std::vector<double> wp(total * 3);
+    std::vector<int32_t> off(n + 1, 0);
+    size_t w = 0;
+    for (size_t k = 0; k < n; ++k) {
+        for (const Vec3& p : sets[k]) {
+            wp[3 * w] = p.x;
+            wp[3 * w + 1] = p.y;
+            wp[3 * w + 2] = p.z;
+            ++w;
+        }
+        off[k + 1] = (int32_t)w;
+    }
+    struct Dev {  // released on every way out
+        void* buf = nullptr;
+        void* st = nullptr;
+        ~Dev() {
+            if (st) (void)epp_stream_destroy(st);
+            if (buf) (void)epp_free(buf);
+        }
+    } d;
+    auto need = [what](epp_status rc) {
+        if (rc == EPP_ERR_INVALID_ARGUMENT) throw std::invalid_argument(epp_last_error());
+        if (rc != EPP_OK) throw std::runtime_error(std::string(what) + ": " + epp_last_error());
+    };
+    auto after = [](size_t o, size_t b) { return (o + b + 255) & ~(size_t)255; };  // 256-B aligned parts
+    const size_t o_wp = 0, o_T = after(o_wp, total * 24), o_C = after(o_T, nseg * 8), o_ft = after(o_C, nseg * 240),
+                 o_fi = after(o_ft, n * 8), o_ct = after(o_fi, n * 8), o_ci = after(o_ct, n * 8),
+                 o_off = after(o_ci, n * 8), o_st = after(o_off, (n + 1) * 4), bytes = after(o_st, n * 4);
+    need(epp_malloc(&d.buf, bytes));
+    need(epp_stream_create(&d.st));
+    char* base = static_cast<char*>(d.buf);
+    need(epp_memcpy_h2d_async(base + o_wp, wp.data(), total * 24, d.st));
+    need(epp_memcpy_h2d_async(base + o_off, off.data(), (n + 1) * 4, d.st));
+    double* d_T = reinterpret_cast<double*>(base + o_T);
+    double* d_C = reinterpret_cast<double*>(base + o_C);
+    const int32_t* d_off = reinterpret_cast<const int32_t*>(base + o_off);
+    need(epp_minsnap_batch(reinterpret_cast<const double*>(base + o_wp), d_off, (int32_t)n, v_max, a_max, nullptr,
+                           nullptr, d_T, d_C, reinterpret_cast<int32_t*>(base + o_st), d.st));
+    if (clr)  // (the chord slots hold the clearance and the nearest OBB)
+        need(epp_traj_clearance_batch(world, d_T, d_C, d_off, (int32_t)n, dt, reinterpret_cast<double*>(base + o_ct),
+                                      reinterpret_cast<int64_t*>(base + o_fi), reinterpret_cast<double*>(base + o_ft),
+                                      reinterpret_cast<int32_t*>(base + o_ci), d.st));
+    else
+        need(epp_traj_check_batch(world, d_T, d_C, d_off, (int32_t)n, dt, minDistance,
+                                  reinterpret_cast<int64_t*>(base + o_fi), reinterpret_cast<double*>(base + o_ft),
+                                  d.st));
+    if (chords)
+        need(epp_traj_sweep_batch(world, d_T, d_C, d_off, (int32_t)n, dt, canPassGate,
+                                  reinterpret_cast<int64_t*>(base + o_ci), reinterpret_cast<double*>(base + o_ct),
+                                  d.st));
+    std::vector<int32_t> status(n);
+    std::vector<int64_t> rows(n), crows(n);
+    std::vector<double> times(n), ctimes(n);
+    need(epp_memcpy_d2h_async(status.data(), base + o_st, n * 4, d.st));
+    need(epp_memcpy_d2h_async(rows.data(), base + o_fi, n * 8, d.st));
+    need(epp_memcpy_d2h_async(times.data(), base + o_ft, n * 8, d.st));
+    if (chords) {
+        need(epp_memcpy_d2h_async(crows.data(), base + o_ci, n * 8, d.st));
+        need(epp_memcpy_d2h_async(ctimes.data(), base + o_ct, n * 8, d.st));
+    }
+    std::vector<int32_t> near(clr ? n : 0);
+    if (clr) {
+        need(epp_memcpy_d2h_async(clr->clearance.data(), base + o_ct, n * 8, d.st));
+        need(epp_memcpy_d2h_async(near.data(), base + o_ci, n * 4, d.st));
+    }
+    need(epp_stream_sync(d.st));
+    for (size_t k = 0; k < n; ++k)
+        if (status[k] != 0)
+            throw std::runtime_error("generateTrajectory: the fit of waypoint set " + std::to_string(k) +
+                                     " failed (status " + std::to_string(status[k]) + ")");
+    for (size_t k = 0; k < n; ++k) {
+        firstInvalidRow[k] = (long)rows[k];
+        if (chords) (*chords)[k] = (long)crows[k];
+    }
+    if (rowTimes) *rowTimes = times;
+    if (chords && chordTimes) *chordTimes = ctimes;
+    if (clr && clr->nearest) clr->nearest->assign(near.begin(), near.end());
+}
+}  // namespace
+
+void PathPlanner::candidateClearances(const std::vector<std::vector<Vec3>>& sets, double v_max, double a_max, double dt,
+                                      std::vector<double>& clearance, std::vector<long>* row,
+                                      std::vector<double>* time, std::vector<int>* nearest) const {
+    std::vector<long> rows;
+    const CandidateClear clr{clearance, nearest};
+    fit_and_check_candidates("candidateClearances", sets.empty() ? nullptr : worldPtr->device(), sets, v_max, a_max,
+                             dt, 0.0, 0, rows, time, nullptr, nullptr, &clr);
+    if (row) *row = rows;
+}
+
+bool PathPlanner::checkCandidateTrajectories(const std::vector<std::vector<Vec3>>& sets, double v_max, double a_max,
+                                             double dt, double minDistance, std::vector<long>& firstInvalidRow,
+                                             std::vector<double>* firstInvalidTime) const {
+    fit_and_check_candidates("checkCandidateTrajectories", sets.empty() ? nullptr : worldPtr->device(), sets, v_max,
+                             a_max, dt, minDistance, 0, firstInvalidRow, firstInvalidTime, nullptr, nullptr);
+    for (long r : firstInvalidRow)
+        if (r >= 0) return false;
+    return true;
+}
+
+bool PathPlanner::sweepCandidateTrajectories(const std::vector<std::vector<Vec3>>& sets, double v_max, double a_max,
+                                             double dt, double minDistance, bool canPassGate,
+                                             std::vector<long>& firstInvalidRow, std::vector<long>& firstInvalidChord,
+                                             std::vector<double>* firstInvalidTime) const {
+    std::vector<double> rowTimes, chordTimes;
+    fit_and_check_candidates("sweepCandidateTrajectories", sets.empty() ? nullptr : worldPtr->device(), sets, v_max,
+                             a_max, dt, minDistance, canPassGate ? 1 : 0, firstInvalidRow, &rowTimes,
+                             &firstInvalidChord, &chordTimes);
+    bool all = true;
+    if (firstInvalidTime) firstInvalidTime->assign(sets.size(), -1.0);
+    for (size_t k = 0; k < sets.size(); ++k) {
+        const long r = firstInvalidRow[k], c = firstInvalidChord[k];
+        all = all && r < 0 && c < 0;
+        // the earlier of the two findings (a failing row j and a failing chord j start at the same time)
+        if (firstInvalidTime && (r >= 0 || c >= 0))
+            (*firstInvalidTime)[k] = (c < 0 || (r >= 0 && r <= c)) ? rowTimes[k] : chordTimes[k];
+    }
+    return all;
+}
+
+}  // namespace epp

@@ -16,7 +16,6 @@
 #include <cstdint>
 #include <memory>
 #include <string>
-#include <functional>
 #include <vector>
 
 #include "epp/ConfigParser.h"
@@ -202,15 +201,6 @@ private:
     void planChunk(const std::vector<std::pair<Vec3, Vec3>>& problems, const std::vector<uint64_t>& seeds,
                    int64_t samples, std::vector<std::vector<Vec3>>& paths, std::vector<char>& ok,
                    GateEnds* ends = nullptr) const;
-    // rows_sym (optional): the caller's symmetrised search on its restricted rows, run while
-    // the device builds the whole table's masked k-NN; when that shows no kept edge into the
-    // goal and rows_sym found the path, *decided_on_rows = true and the table is neither
-    // downloaded nor searched (the caller takes its own path); *census_goal_edges (with
-    // rows_sym): the whole table's kept edges into the goal
-    bool wholeTableSearch(const double* d_nodes, int32_t n, const double box_lo[3], const double box_hi[3], void* area,
-                          std::vector<Vec3>& path, int64_t& edges_checked, int64_t& edges_valid, double& ms_dev,
-                          double& ms_search, const std::function<bool()>* rows_sym = nullptr,
-                          bool* decided_on_rows = nullptr, int64_t* census_goal_edges = nullptr) const;
 
     std::shared_ptr<ConfigParser> configParser;
     uint64_t seed_ = 0x5eedull;

@@ -120,7 +120,8 @@ void or_random_vertices(int n_segments, int dim, double pos_min, double pos_max,
                         double* out);
 
 /* ---- CPU restatement of this build's batch planner ------------------------- */
-/* One attempt of PathPlanner::planOnce (efficient-path-planner_amd/csrc/host_planner.cpp)
+/* One attempt of PathPlanner::planOnce (efficient-path-planner_amd/csrc/host_planner.cpp;
+ * the searches: csrc/graph_search.h, the shortcut: csrc/host_simplify.cpp)
  * on `threads` host threads: counter-RNG samples in [lo, hi], state checks, ordered
  * compaction (nodes = start, goal, valid samples), exact k-NN (ties to the lower index),
  * motion checks, A* (forward edges, then symmetrised), greedy shortcut.  Writes the path

@@ -1,5 +1,5 @@
 """Diagnostics: the symmetrised search on the restricted rows after the whole table's goal-edge
-count (host_planner.cpp solve) against the whole-table search, timed on goals outside the
+count (host_plan_solve.cpp census) against the whole-table search, timed on goals outside the
 sampling box (the C4 box, track world 100, 65,536 samples): plan_once per seed, the
 planner's own split."""
 import json

@@ -37,8 +37,8 @@ if len(sys.argv) > 1 and sys.argv[1] == "--child":
         ts.append((time.perf_counter() - t) * 1e3)
         st.append(otg.planner_stats())
     os.unlink(path)
-    print(f"{os.path.basename(os.environ.get('EPP_PKG', '') or 'cur')} threads {os.environ.get('EPP_PLAN_THREADS', '4')} writer {os.environ.get('EPP_PATH_WRITER', '1')}: pre_compute_traj p50 {np.median(ts):.2f} ms "
-          f"(mean {np.mean(ts):.2f}, min {min(ts):.2f}); planner: ms {np.median([s['ms'] for s in st]):.2f}, device sum "
+    print(f"{os.path.basename(os.environ.get('EPP_PKG', '') or 'cur')} threads {os.environ.get('EPP_PLAN_THREADS', '4')} writer {os.environ.get('EPP_PATH_WRITER', '1')}: pre_compute_traj p50 {np.median(ts):.4f} ms "
+          f"(mean {np.mean(ts):.2f}, min {min(ts):.2f}); planner: ms {np.median([s['ms'] for s in st]):.4f}, device sum "
           f"{np.median([s['ms_device'] for s in st]):.2f}, search sum {np.median([s['ms_search'] for s in st]):.2f}, "
           f"rows down per track {np.median([s['rows_downloaded'] for s in st]):.0f} "
           f"(EPP_PLAN_ELLIPSE {os.environ.get('EPP_PLAN_ELLIPSE', 'default')})",

@@ -846,7 +846,7 @@ def test_plan_once_symmetrised_on_rows_equals_cpu(bench_track_config, geom):
     """Goals outside the sampling box (the C4 box, track world 100, 65,536 samples): no
     sample keeps the goal among its 16 neighbours, so the forward search fails and the
     symmetrised graph (the goal's own row, reversed) decides.  The planner runs that search
-    on the downloaded rows (host_planner.cpp solve, `restricted_symmetrised`) instead of the
+    on the downloaded rows (host_plan_solve.cpp, `restricted_symmetrised`) instead of the
     whole table -- here after the whole table's masked k-NN showed no kept edge into the
     goal (the forward search popped above the bound: `symmetrised_after_census`); the path
     equals the CPU restatement's, whose stats say its symmetrised search ran."""
