@@ -256,6 +256,61 @@ PYBIND11_MODULE(online_traj_planner, m) {
             },
             py::arg("points"))
         .def(
+            "candidate_first_hits",  // fit + first hit of the first failing chord of K waypoint sets (this build)
+            [](const epp::PathPlanner& self, const std::vector<py::object>& waypointSets, double vMax, double aMax,
+               double samplingInterval, bool canPassGate) {
+                std::vector<std::vector<Vec3>> sets;
+                for (const auto& o : waypointSets) {
+                    Matrix w = to_matrix(o);
+                    if (w.cols != 3) throw std::invalid_argument("waypoints must be an (n, 3) array");
+                    std::vector<Vec3> wp;
+                    for (size_t i = 0; i < w.rows; ++i) wp.emplace_back(w(i, 0), w(i, 1), w(i, 2));
+                    sets.push_back(std::move(wp));
+                }
+                std::vector<double> hits, times;
+                std::vector<long> chords;
+                std::vector<int> obbs;
+                {
+                    py::gil_scoped_release release;
+                    self.candidateFirstHits(sets, vMax, aMax, samplingInterval, canPassGate, chords, hits, &times, &obbs);
+                }
+                py::array_t<int64_t> c((py::ssize_t)chords.size());
+                py::array_t<double> h((py::ssize_t)hits.size()), t((py::ssize_t)times.size());
+                py::array_t<int32_t> o((py::ssize_t)obbs.size());
+                for (size_t i = 0; i < chords.size(); ++i) {
+                    c.mutable_data()[i] = chords[i];
+                    h.mutable_data()[i] = hits[i];
+                    t.mutable_data()[i] = times[i];
+                    o.mutable_data()[i] = obbs[i];
+                }
+                return py::make_tuple(c, h, t, o);
+            },
+            py::arg("waypoint_sets"), py::arg("v_max"), py::arg("a_max"), py::arg("sampling_interval"),
+            py::arg("can_pass_gate") = false)
+        .def(
+            "first_hits",  // where every edge s1[i] -> s2[i] is first blocked, and by which OBB (this build)
+            [](const epp::PathPlanner& self, const py::object& s1, const py::object& s2, bool canPassGate) {
+                Matrix a = to_matrix(s1), b = to_matrix(s2);
+                if (a.cols != 3 || b.cols != 3 || a.rows != b.rows)
+                    throw std::invalid_argument("s1 and s2 must be (n, 3) arrays of the same length");
+                std::vector<double> x1(a.rows * 3), x2(a.rows * 3);
+                for (size_t i = 0; i < a.rows; ++i)
+                    for (size_t k = 0; k < 3; ++k) {
+                        x1[3 * i + k] = a(i, k);
+                        x2[3 * i + k] = b(i, k);
+                    }
+                py::array_t<double> t((py::ssize_t)a.rows);
+                py::array_t<int32_t> o((py::ssize_t)a.rows);
+                double* tp = t.mutable_data();
+                int32_t* op = o.mutable_data();
+                {
+                    py::gil_scoped_release release;
+                    self.worldPtr->firstHits(x1.data(), x2.data(), (int64_t)a.rows, canPassGate, tp, op);
+                }
+                return py::make_tuple(t, o);
+            },
+            py::arg("s1"), py::arg("s2"), py::arg("can_pass_gate") = false)
+        .def(
             "check_point_validity",
             [](const epp::PathPlanner& self, const py::object& p, bool canPassGate) {
                 return self.worldPtr->checkPointValidity(to_vec3(p), canPassGate);

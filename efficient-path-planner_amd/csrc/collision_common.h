@@ -514,7 +514,16 @@ __device__ __forceinline__ bool states_exact_pt(const unsigned char* sbase, uint
 // the slab test always (:28).  Axes are processed in order with the reference's min /
 // max selects; an axis after a rejection cannot undo it, so evaluating every axis and
 // combining the rejections gives the reference's early-return answer.
-__device__ __forceinline__ bool rec_ray_hit(const double* rec, const double s[3], const double e[3], double r) {
+// PARTS: the sub-answers are also kept apart in *parts (first_hit.h needs them): the two
+// endpoint tests, the final predicate on tMin / tMax (:60) and tMin itself, the entry
+// parameter when slab_hit.  The same operations either way: one body.
+struct RayParts {
+    bool start_hit, end_hit, slab_hit;
+    double tMin;
+};
+template <bool PARTS>
+__device__ __forceinline__ bool rec_ray_core(const double* rec, const double s[3], const double e[3], double r,
+                                             RayParts* parts) {
     double f[kRecDoubles];
 #pragma unroll
     for (int k = 0; k <= F_HZ; ++k) f[k] = rec[k];
@@ -537,6 +546,10 @@ __device__ __forceinline__ bool rec_ray_hit(const double* rec, const double s[3]
         const double le0 = c * ex + sn * ey, le1 = c * ey - sn * ex;
         end_hit = ((fabs(ls[0]) <= ph0) & (fabs(ls[1]) <= ph1) & (fabs(dz) <= ph2)) |
                   ((fabs(le0) <= ph0) & (fabs(le1) <= ph1) & (fabs(ez) <= ph2));
+        if (PARTS) {
+            parts->start_hit = (fabs(ls[0]) <= ph0) & (fabs(ls[1]) <= ph1) & (fabs(dz) <= ph2);
+            parts->end_hit = (fabs(le0) <= ph0) & (fabs(le1) <= ph1) & (fabs(ez) <= ph2);
+        }
         ld[0] = le0 - ls[0];  // localEnd - localStart  :23
         ld[1] = le1 - ls[1];
         ld[2] = ez - ls[2];
@@ -565,7 +578,19 @@ __device__ __forceinline__ bool rec_ray_hit(const double* rec, const double s[3]
         tMax = par ? tMax : nMax;
     }
     const bool slab_hit = !rejected & (0 <= tMin) & (tMin <= 1) & (0 <= tMax) & (tMax <= 1);  // :60
+    if (PARTS) {
+        parts->slab_hit = slab_hit;
+        parts->tMin = tMin;
+    }
     return end_hit | slab_hit;
+}
+__device__ __forceinline__ bool rec_ray_hit(const double* rec, const double s[3], const double e[3], double r) {
+    return rec_ray_core<false>(rec, s, e, r, nullptr);
+}
+__device__ __forceinline__ RayParts rec_ray_parts(const double* rec, const double s[3], const double e[3], double r) {
+    RayParts p;
+    (void)rec_ray_core<true>(rec, s, e, r, &p);
+    return p;
 }
 
 struct DevInfo {

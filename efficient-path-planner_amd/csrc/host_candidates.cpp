@@ -94,16 +94,22 @@ namespace {
 // `what` names the caller in the errors.  clr != nullptr: instead of the two checks, the
 // closest approach of every fitted track's rows (epp_traj_clearance_batch) into *clr, the row
 // into firstInvalidRow and its time into rowTimes -- the same upload, fit, stream and single
-// synchronisation.
+// synchronisation.  hit != nullptr: likewise the first hit of every fitted track
+// (epp_traj_first_hit_batch): the entry parameter into *hit, the chord into firstInvalidRow
+// and the hit's time into rowTimes.
 struct CandidateClear {
     std::vector<double>& clearance;
     std::vector<int>* nearest;
+};
+struct CandidateHit {
+    std::vector<double>& t;
+    std::vector<int>* obb;
 };
 void fit_and_check_candidates(const char* what, const epp_world* world, const std::vector<std::vector<Vec3>>& sets,
                               double v_max, double a_max, double dt, double minDistance, int32_t canPassGate,
                               std::vector<long>& firstInvalidRow, std::vector<double>* rowTimes,
                               std::vector<long>* chords, std::vector<double>* chordTimes,
-                              const CandidateClear* clr = nullptr) {
+                              const CandidateClear* clr = nullptr, const CandidateHit* hit = nullptr) {
     for (const auto& s : sets)
         if (s.size() < 2) throw std::invalid_argument("At least two waypoints are required");
     const size_t n = sets.size();
@@ -114,6 +120,10 @@ void fit_and_check_candidates(const char* what, const epp_world* world, const st
     if (clr) {
         clr->clearance.assign(n, HUGE_VAL);
         if (clr->nearest) clr->nearest->assign(n, -1);
+    }
+    if (hit) {
+        hit->t.assign(n, HUGE_VAL);
+        if (hit->obb) hit->obb->assign(n, -1);
     }
     if (n == 0) return;
     // host image of the upload: [waypoints | offsets]; device block: [wp | T | coeffs |
@@ -163,6 +173,11 @@ void fit_and_check_candidates(const char* what, const epp_world* world, const st
         need(epp_traj_clearance_batch(world, d_T, d_C, d_off, (int32_t)n, dt, reinterpret_cast<double*>(base + o_ct),
                                       reinterpret_cast<int64_t*>(base + o_fi), reinterpret_cast<double*>(base + o_ft),
                                       reinterpret_cast<int32_t*>(base + o_ci), d.st));
+    else if (hit)  // (the chord slots hold the entry parameter and the OBB)
+        need(epp_traj_first_hit_batch(world, d_T, d_C, d_off, (int32_t)n, dt, canPassGate,
+                                      reinterpret_cast<int64_t*>(base + o_fi), reinterpret_cast<double*>(base + o_ct),
+                                      reinterpret_cast<double*>(base + o_ft), reinterpret_cast<int32_t*>(base + o_ci),
+                                      d.st));
     else
         need(epp_traj_check_batch(world, d_T, d_C, d_off, (int32_t)n, dt, minDistance,
                                   reinterpret_cast<int64_t*>(base + o_fi), reinterpret_cast<double*>(base + o_ft),
@@ -181,9 +196,9 @@ void fit_and_check_candidates(const char* what, const epp_world* world, const st
         need(epp_memcpy_d2h_async(crows.data(), base + o_ci, n * 8, d.st));
         need(epp_memcpy_d2h_async(ctimes.data(), base + o_ct, n * 8, d.st));
     }
-    std::vector<int32_t> near(clr ? n : 0);
-    if (clr) {
-        need(epp_memcpy_d2h_async(clr->clearance.data(), base + o_ct, n * 8, d.st));
+    std::vector<int32_t> near(clr || hit ? n : 0);
+    if (clr || hit) {
+        need(epp_memcpy_d2h_async((clr ? clr->clearance : hit->t).data(), base + o_ct, n * 8, d.st));
         need(epp_memcpy_d2h_async(near.data(), base + o_ci, n * 4, d.st));
     }
     need(epp_stream_sync(d.st));
@@ -198,8 +213,17 @@ void fit_and_check_candidates(const char* what, const epp_world* world, const st
     if (rowTimes) *rowTimes = times;
     if (chords && chordTimes) *chordTimes = ctimes;
     if (clr && clr->nearest) clr->nearest->assign(near.begin(), near.end());
+    if (hit && hit->obb) hit->obb->assign(near.begin(), near.end());
 }
 }  // namespace
+
+void PathPlanner::candidateFirstHits(const std::vector<std::vector<Vec3>>& sets, double v_max, double a_max, double dt,
+                                     bool canPassGate, std::vector<long>& chord, std::vector<double>& t,
+                                     std::vector<double>* time, std::vector<int>* obb) const {
+    const CandidateHit hit{t, obb};
+    fit_and_check_candidates("candidateFirstHits", sets.empty() ? nullptr : worldPtr->device(), sets, v_max, a_max, dt,
+                             0.0, canPassGate ? 1 : 0, chord, time, nullptr, nullptr, nullptr, &hit);
+}
 
 void PathPlanner::candidateClearances(const std::vector<std::vector<Vec3>>& sets, double v_max, double a_max, double dt,
                                       std::vector<double>& clearance, std::vector<long>* row,

@@ -203,6 +203,26 @@ void World::clearance(const double* xyz, int64_t n, double* dist, int32_t* neare
     if (nearest) std::memcpy(nearest, out.data() + (size_t)n * 8, (size_t)n * 4);
 }
 
+void World::firstHits(const double* s1, const double* s2, int64_t n, bool canPassGate, double* t, int32_t* obb) const {
+    if (n <= 0) return;
+    if (!device()) {  // an empty world: nothing blocks
+        for (int64_t i = 0; i < n; ++i) {
+            t[i] = HUGE_VAL;
+            if (obb) obb[i] = -1;
+        }
+        return;
+    }
+    // one output block per call: [t (n f64) | obb (n i32)], 12 bytes per query
+    const double* in[2] = {s1, s2};
+    std::vector<uint8_t> out((size_t)n * 12);
+    query(n, 2, [&](const double* const* d, uint8_t* o, void* st) {
+        check(epp_motions_first_hit(device(), d[0], d[1], n, canPassGate ? 1 : 0, reinterpret_cast<double*>(o),
+                                    reinterpret_cast<int32_t*>(o + (size_t)n * 8), st), "firstHits");
+    }, [](const double* const*, uint8_t*, void*) { return false; }, in, out.data(), 12);
+    std::memcpy(t, out.data(), (size_t)n * 8);
+    if (obb) std::memcpy(obb, out.data() + (size_t)n * 8, (size_t)n * 4);
+}
+
 template <typename Launch, typename Small>
 void World::query(int64_t n, int n_in, Launch&& launch, Small&& small, const double* const* in, uint8_t* out,
                   size_t out_item) const {

@@ -1,7 +1,8 @@
 // trajcheck.hip — first collision of fitted trajectories, straight from their coefficients
 // (gfx950): of their rows (k_traj_check) and of the chords between the rows (k_traj_sweep);
 // and the clearance of their rows (k_traj_clearance, below: the closest approach to a
-// collision OBB, where and against which), on the same walk.
+// collision OBB, where and against which), on the same walk; and the first hit of the first
+// failing chord (k_traj_first_hit, below: how far into the chord and against which OBB).
 //
 //   PathPlanner::checkTrajectoryValidity  src/PathPlanner.cpp:267-280, per track, over the rows
 //   Trajectory::evaluateRange(0, max_time, dt)  src/trajectory.cpp:81-141 would produce, with
@@ -31,6 +32,7 @@
 
 #include "clearance.h"
 #include "collision_common.h"
+#include "first_hit.h"
 #include "traj_sample.h"
 
 namespace epp {
@@ -95,6 +97,8 @@ __device__ __forceinline__ Acc tc_stage(const WorldView& w, unsigned char* lds, 
 //   keep(s, b)                      thread 0, before it overwrites half b ^ 1
 //   check(s, b, cnt, base, lane, coeffs, seg0)   wave 1: atomicMin(&s.first[b], j) for a failing j
 //   row(f), time(s, b, f)           the answer for posted sample f of half b, relative to base
+//   posted(s, b, f, coeffs, seg0)   every thread, once per track with a posted sample, while
+//                                   half b is still intact: what a check adds to that answer
 //   end(t, tid, walked, res, rtime, first_invalid, first_time)   the track is over (every thread;
 //                                   walked: it had a segment): write its outputs.  A check that
 //                                   never posts walks every chunk and answers from its own state.
@@ -154,6 +158,7 @@ __device__ __forceinline__ void tc_walk(TcShared& s, const double* __restrict__ 
                 if (f != INT_MAX) {
                     res = base + chk.row(f);
                     rtime = chk.time(s, b, f) + 0.0;  // epp_sample_batch's time column with t0 == NULL
+                    chk.posted(s, b, f, coeffs, seg0);
                     break;
                 }
                 if (done) break;
@@ -167,6 +172,7 @@ __device__ __forceinline__ void tc_walk(TcShared& s, const double* __restrict__ 
 
 // How the two first-failure checks end a track: thread 0 writes the walk's answer.
 struct TcFirst {
+    __device__ __forceinline__ void posted(const TcShared&, int, int, const double* __restrict__, int) {}
     __device__ __forceinline__ void end(int t, int tid, bool, int64_t res, double rtime,
                                         int64_t* __restrict__ first_invalid, double* __restrict__ first_time) {
         if (tid == 0) {
@@ -263,6 +269,77 @@ struct TcChords : TcFirst {
     }
 };
 
+// The first hit of the first failing chord (first_hit.h): TcChords finds the chord -- its own
+// check, row and time, so the chord is epp_traj_sweep_batch's by construction -- and, once per
+// track and only after a chord was posted, the checking wave answers where the chord row j ->
+// row j + 1 is first blocked and by which OBB: every lane evaluates the two row positions
+// (tc_pos: the bits the detection tested), lanes stride over all records of the world through
+// L2 keeping a strict < minimum (a lane's indices ascend), and the wave min-reduces
+// lexicographically on (t, index).  The chord's start row for a posted sample 0 is the
+// previous chunk's last position, which check() is about to overwrite: it is kept (ox, oy, oz),
+// and so is that row's time (otac: TcChords' prev_tac is thread 0's alone).
+// time = t_j + t_hit * (t_j+1 - t_j) on the time columns epp_sample_batch writes with
+// t0 == NULL.  A track without a failing chord keeps +inf, -1.0, -1.
+struct TcHitOut {
+    int can_pass;
+    double* t_hit;
+    double* time;
+    int32_t* obb;
+};
+struct TcFirstHit : TcChords {
+    TcHitOut out;
+    double ox, oy, oz;  // wave 1: the last position of the chunk before the one being checked
+    double otac, ctac;  // wave 1: that row's time; the same for the chunk being checked
+    double ht, htime;   // wave 1: the track's answer
+    int hobb;
+    __device__ __forceinline__ void reset() {
+        ht = HUGE_VAL;
+        htime = -1.0;
+        hobb = -1;
+    }
+    __device__ __forceinline__ void check(TcShared& s, int b, int cnt, int64_t base, int lane,
+                                          const double* __restrict__ coeffs, int seg0) {
+        ox = cx;
+        oy = cy;
+        oz = cz;
+        otac = ctac;
+        ctac = s.tac[b][kRowChunk - 1];  // (a full chunk's last row; else no chunk follows)
+        TcChords::check(s, b, cnt, base, lane, coeffs, seg0);
+    }
+    __device__ __forceinline__ void posted(const TcShared& s, int b, int f, const double* __restrict__ coeffs,
+                                           int seg0) {
+        if (threadIdx.x < 64) return;  // (wave-uniform: the checking wave)
+        const int lane = threadIdx.x - 64;
+        double q[3] = {ox, oy, oz}, e[3];
+        if (f > 0) tc_pos(s, b, f - 1, coeffs, seg0, q);
+        tc_pos(s, b, f, coeffs, seg0, e);
+        HitEdge g;
+        g.set(q[0], q[1], q[2], e[0], e[1], e[2]);
+        const double* recs = reinterpret_cast<const double*>(w.blob + w.off_aos);
+        hit_min(recs, lane, w.n_obb, kTcCheckers, 0, g, w.r_gate, w.r_obst, cp, ht, hobb);
+        for (int m = 32; m > 0; m >>= 1) {
+            const double ot = __shfl_xor(ht, m);
+            const int oo = __shfl_xor(hobb, m);
+            const bool take = ot < ht || (ot == ht && oo < hobb);
+            ht = take ? ot : ht;
+            hobb = take ? oo : hobb;
+        }
+        // the two rows' time columns as epp_sample_batch writes them with t0 == NULL
+        const double t0 = (f > 0 ? s.tac[b][f - 1] : otac) + 0.0, t1 = s.tac[b][f] + 0.0;
+        htime = t0 + ht * (t1 - t0);
+    }
+    __device__ __forceinline__ void end(int t, int tid, bool walked, int64_t res, double rtime,
+                                        int64_t* __restrict__ chord, double* __restrict__ first_time) {
+        TcFirst::end(t, tid, walked, res, rtime, chord, first_time);
+        if (tid == 64) {
+            out.t_hit[t] = ht;
+            if (out.time) out.time[t] = htime;
+            if (out.obb) out.obb[t] = hobb;
+        }
+        reset();
+    }
+};
+
 // The clearance of the rows: the minimum over a track's rows of the squared distance to the
 // nearest collision OBB (clearance.h), where it is attained and against which OBB.  Nothing is
 // ever posted to first[], so the walk visits every chunk of every track.  A checking lane
@@ -310,6 +387,7 @@ struct TcClear {
     }
     __device__ __forceinline__ int row(int f) const { return f; }                           // (never posted:
     __device__ __forceinline__ double time(const TcShared&, int, int) const { return 0.0; }  //  never asked)
+    __device__ __forceinline__ void posted(const TcShared&, int, int, const double* __restrict__, int) {}
     __device__ __forceinline__ void end(int t, int tid, bool walked, int64_t, double, int64_t* __restrict__ row_out,
                                         double* __restrict__ time_out) {
         if (tid < 64) return;  // (wave-uniform: wave 1 holds the bests)
@@ -373,6 +451,35 @@ __global__ __launch_bounds__(kTcBlock) void k_traj_sweep(WorldView w, const doub
             TcChords{{}, a, w, can_pass != 0});
 }
 
+template <int STAGE>
+__global__ __launch_bounds__(kTcBlock) void k_traj_first_hit(WorldView w, const double* __restrict__ seg_times,
+                                                             const double* __restrict__ coeffs,
+                                                             const int32_t* __restrict__ wp_off, int n_tracks,
+                                                             double dt, TcHitOut out, int64_t* __restrict__ chord,
+                                                             double* __restrict__ first_time, uint32_t stage_bytes) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    const Acc a = tc_stage<STAGE>(w, lds, stage_bytes);
+    TcFirstHit chk{{{}, a, w, out.can_pass != 0}, out};
+    chk.reset();
+    tc_walk(*reinterpret_cast<TcShared*>(lds), seg_times, coeffs, wp_off, n_tracks, dt, chord, first_time, chk);
+}
+
+// What the ray walk of the chords reads short of the SoA table (cell starts, cell lists, meta
+// words) in LDS when it fits, else the front alone, else nothing.  EPP_TRAJSWEEP_STAGE = 0 | 1
+// caps the level (A/B and test knob): 0 reads the whole world through L2.
+int sweep_stage(const WorldView& v, uint32_t& bytes) {
+    const int cap = env_int("EPP_TRAJSWEEP_STAGE", 2);
+    if (cap >= 2 && v.off_soa % 16 == 0 && v.off_soa <= kTcWorldLds) {
+        bytes = v.off_soa;
+        return 2;
+    }
+    if (cap >= 1 && v.front_bytes <= kTcWorldLds) {
+        bytes = v.front_bytes;
+        return 1;
+    }
+    return 0;
+}
+
 // What both entry points do around their kernels.  P: the check's own parameter (kernel
 // argument 7); ok: the entry point's own argument checks (its required output among them); kernels: its kernel per staging
 // level; stage(view, bytes): the level for this world, and how many bytes it stages.
@@ -431,25 +538,20 @@ epp_status epp_traj_sweep_batch(const epp_world* world, const double* seg_times,
                                 const int32_t* wp_offsets, int32_t n_tracks, double dt, int32_t can_pass_gate,
                                 int64_t* first_invalid, double* first_time, void* stream) {
     static constexpr TcKernel<int> kernels[] = {k_traj_sweep<0>, k_traj_sweep<1>, k_traj_sweep<2>};
-    // What the ray walk reads short of the SoA table (cell starts, cell lists, meta words) in
-    // LDS when it fits, else the front alone, else nothing.  EPP_TRAJSWEEP_STAGE = 0 | 1 caps
-    // the level (A/B and test knob): 0 reads the whole world through L2.
-    const auto stage = [](const WorldView& v, uint32_t& bytes) {
-        const int cap = env_int("EPP_TRAJSWEEP_STAGE", 2);
-        if (cap >= 2 && v.off_soa % 16 == 0 && v.off_soa <= kTcWorldLds) {
-            bytes = v.off_soa;
-            return 2;
-        }
-        if (cap >= 1 && v.front_bytes <= kTcWorldLds) {
-            bytes = v.front_bytes;
-            return 1;
-        }
-        return 0;
-    };
     return tc_launch("epp_traj_sweep_batch", (can_pass_gate == 0 || can_pass_gate == 1) && (n_tracks <= 0 || first_invalid),
-                     kernels, stage, world,
+                     kernels, sweep_stage, world,
                      seg_times, coeffs, wp_offsets, n_tracks, dt, (int)can_pass_gate, first_invalid, first_time,
                      stream);
+}
+
+epp_status epp_traj_first_hit_batch(const epp_world* world, const double* seg_times, const double* coeffs,
+                                    const int32_t* wp_offsets, int32_t n_tracks, double dt, int32_t can_pass_gate,
+                                    int64_t* chord, double* t_hit, double* time, int32_t* obb, void* stream) {
+    static constexpr TcKernel<TcHitOut> kernels[] = {k_traj_first_hit<0>, k_traj_first_hit<1>, k_traj_first_hit<2>};
+    return tc_launch("epp_traj_first_hit_batch",
+                     (can_pass_gate == 0 || can_pass_gate == 1) && (n_tracks <= 0 || (chord && t_hit)), kernels,
+                     sweep_stage, world, seg_times, coeffs, wp_offsets, n_tracks, dt,
+                     TcHitOut{(int)can_pass_gate, t_hit, time, obb}, chord, nullptr, stream);
 }
 
 epp_status epp_traj_clearance_batch(const epp_world* world, const double* seg_times, const double* coeffs,

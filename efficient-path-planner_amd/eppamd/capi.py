@@ -99,6 +99,8 @@ def lib() -> C.CDLL:
             "epp_traj_sweep_batch": (i32, [vp, vp, vp, vp, i32, dp, i32, vp, vp, vp]),
             "epp_states_clearance": (i32, [vp, vp, i64, vp, vp, vp]),
             "epp_traj_clearance_batch": (i32, [vp, vp, vp, vp, i32, dp, vp, vp, vp, vp, vp]),
+            "epp_motions_first_hit": (i32, [vp, vp, vp, i64, i32, vp, vp, vp]),
+            "epp_traj_first_hit_batch": (i32, [vp, vp, vp, vp, i32, dp, i32, vp, vp, vp, vp, vp]),
             "epp_generate_trajectory_limited_host": (i32, [vp, i32, dp, dp, dp, dp, vp, vp,
                                                            C.POINTER(C.POINTER(C.c_double)), C.POINTER(i64),
                                                            C.POINTER(C.c_double)]),
@@ -159,6 +161,7 @@ EXPORTED = [
     "epp_comm_set_timeout", "epp_comm_abort", "epp_check_and_generate_trajectory_host",
     "epp_traj_peaks", "epp_traj_scale_to_limits", "epp_generate_trajectory_limited_host",
     "epp_traj_check_batch", "epp_traj_sweep_batch", "epp_states_clearance", "epp_traj_clearance_batch",
+    "epp_motions_first_hit", "epp_traj_first_hit_batch",
 ]
 
 
@@ -376,6 +379,39 @@ class World:
         sync()
         return (d_clr.download(np.float64, nt), d_row.download(np.int64, nt), d_time.download(np.float64, nt),
                 d_near.download(np.int32, nt))
+
+    def first_hits(self, s1: np.ndarray, s2: np.ndarray, can_pass_gate: bool = False):
+        """epp_motions_first_hit: per edge s1[i] -> s2[i] the parameter in [0, 1] at which it
+        first enters an OBB that World::checkRayValid rejects it for (0: the start is in
+        collision) and that OBB's index in the world's order (the lowest index among equals);
+        (+inf, -1) for an edge check_motions (mode 0) calls valid.  Returns (float64[n],
+        int32[n])."""
+        s1 = np.ascontiguousarray(s1, np.float64).reshape(-1, 3)
+        s2 = np.ascontiguousarray(s2, np.float64).reshape(-1, 3)
+        n = len(s1)
+        assert len(s2) == n
+        d1, d2 = DeviceBuffer.from_array(s1), DeviceBuffer.from_array(s2)
+        d_t, d_obb = DeviceBuffer(8 * n), DeviceBuffer(4 * n)
+        check(lib().epp_motions_first_hit(self.handle, d1.ptr, d2.ptr, n, 1 if can_pass_gate else 0, d_t.ptr,
+                                          d_obb.ptr, None))
+        sync()
+        return d_t.download(np.float64, n), d_obb.download(np.int32, n)
+
+    def trajectory_first_hits(self, Ts, Cs, dt: float, can_pass_gate: bool = False):
+        """epp_traj_first_hit_batch on the lists minsnap_batch returns: per track the first
+        failing chord (sweep_trajectories' answer), the parameter along it at which it enters
+        the blocking OBB, the track time of that point and the OBB; (-1, +inf, -1.0, -1) when
+        no chord fails.  Returns (int64[n], float64[n], float64[n], int32[n])."""
+        nt = len(Ts)
+        d_T, d_C, d_off, _, _ = _upload_tracks(Ts, Cs)
+        d_chord, d_t, d_time, d_obb = (DeviceBuffer(8 * nt), DeviceBuffer(8 * nt), DeviceBuffer(8 * nt),
+                                       DeviceBuffer(4 * nt))
+        check(lib().epp_traj_first_hit_batch(self.handle, d_T.ptr, d_C.ptr, d_off.ptr, nt, float(dt),
+                                             1 if can_pass_gate else 0, d_chord.ptr, d_t.ptr, d_time.ptr, d_obb.ptr,
+                                             None))
+        sync()
+        return (d_chord.download(np.int64, nt), d_t.download(np.float64, nt), d_time.download(np.float64, nt),
+                d_obb.download(np.int32, nt))
 
 
 def minsnap_batch(tracks, v_max, a_max, v0=None, a0=None):

@@ -38,6 +38,10 @@
  *   epp_states_clearance / epp_traj_clearance_batch
  *       no reference counterpart: the Euclidean distance to the nearest collision OBB, per
  *       state and as the closest approach of every fitted track's rows.
+ *   epp_motions_first_hit / epp_traj_first_hit_batch
+ *       what MotionValidator::checkMotion(s1, s2, lastValid) (src/MotionValidator.cpp:19-22, a
+ *       stub there) needs: where along a straight edge World::checkRayValid first fails and
+ *       against which OBB, per edge and for the first failing chord of every fitted track.
  */
 #ifndef EPP_H_
 #define EPP_H_
@@ -307,6 +311,54 @@ epp_status epp_states_clearance(const epp_world* w, const double* xyz, int64_t n
 epp_status epp_traj_clearance_batch(const epp_world* w, const double* seg_times, const double* coeffs,
                                     const int32_t* wp_offsets, int32_t n_tracks, double dt, double* clearance,
                                     int64_t* row, double* time, int32_t* nearest, void* stream);
+
+/* ---- first hit: where a straight edge is first blocked, and by which OBB (device pointers)
+ * For the edge s -> e, can_pass_gate and OBB i with owner radius r (r_gate for a gate's OBB,
+ * r_obst otherwise), the candidates are exactly the OBBs World::checkRayValid
+ * (src/World.cpp:130-162) would test: OBB i takes part iff its stored inflated AABB overlaps
+ * the edge's bounding box [min(s, e), max(s, e)], closed on both sides, and it is not a
+ * filling OBB with can_pass_gate == 1.  On a candidate, OBB::checkCollisionWithRay
+ * (src/OBB.cpp:10-61) is evaluated as by epp_check_motions (mode 0), every operation one IEEE
+ * fp64 multiply, add, subtract or divide in the reference's association, nothing fused:
+ *   start_hit, end_hit   the two endpoint tests (:13-18), inflated by r iff the OBB is not filling
+ *   slab_hit             the final predicate 0 <= tMin <= 1 && 0 <= tMax <= 1 (:60) after the
+ *                        three axes, each inflated by r, without an earlier rejection
+ * and the entry parameter of OBB i is
+ *   t_i = 0.0   if start_hit
+ *         tMin  else if slab_hit
+ *         1.0   else if end_hit   (reachable: an axis with |d| < 1e-6 tests only the start
+ *                                  against its faces, :34-41)
+ *   else OBB i does not block the edge.
+ * t_hit = min_i t_i, and obb is the lowest index i, in the order given to epp_world_create /
+ * epp_world_update, that attains it; +inf and -1 when no OBB blocks the edge.  So obb >= 0
+ * exactly when epp_check_motions (mode 0) gives flag 0 for that edge and can_pass_gate.  The
+ * point s + t_hit (e - s) lies on a closed face of the inflated box and is itself in
+ * collision.  A zero t_hit may carry either sign.  Non-finite endpoints go through the same
+ * operations (NaN compares false); nothing more is promised for them.
+ *
+ * epp_motions_first_hit: t_hit[i] (n, device f64) and obb[i] (n, device int32, may be NULL)
+ * for each of the n edges s1[i] -> s2[i] (n x 3 f64 each).  Every OBB of the world is visited
+ * (no grid or tile filter).  Stream-ordered, no host synchronisation and no allocation; a
+ * stale world index is rebuilt first, as by epp_check_motions, so the call can be captured
+ * (epp_graph_begin) after epp_world_build_index.  EPP_ERR_INVALID_ARGUMENT (before any device
+ * work) for a NULL world, n < 0, can_pass_gate not 0 or 1, or a NULL s1, s2 or t_hit with
+ * n > 0; n == 0 launches nothing. */
+epp_status epp_motions_first_hit(const epp_world* w, const double* s1, const double* s2, int64_t n,
+                                 int32_t can_pass_gate, double* t_hit, int32_t* obb, void* stream);
+/* The first hit of every track of a batch in the layout of epp_minsnap_batch, straight from
+ * the coefficients, in one launch and without writing a row.  chord[k] (n_tracks, device
+ * int64) is epp_traj_sweep_batch's first_invalid[k]: the lowest j whose chord row j -> row
+ * j + 1 fails (the same detection code).  t_hit[k] (device f64) and obb[k] (device int32, may
+ * be NULL) are what epp_motions_first_hit gives for that chord's two row positions, and
+ * time[k] (device f64, may be NULL) = t_j + t_hit * (t_j+1 - t_j) on the time columns
+ * epp_sample_batch writes with t0 == NULL: one subtract, one multiply, one add, unfused.  A
+ * track without a failing chord, or with fewer than two rows, gives -1, +inf, -1.0, -1.
+ * Stream-ordered, no host synchronisation and no allocation; a stale world index is rebuilt
+ * first.  EPP_ERR_INVALID_ARGUMENT as epp_traj_sweep_batch, and for a NULL chord or t_hit
+ * with n_tracks > 0; n_tracks == 0 launches nothing. */
+epp_status epp_traj_first_hit_batch(const epp_world* w, const double* seg_times, const double* coeffs,
+                                    const int32_t* wp_offsets, int32_t n_tracks, double dt, int32_t can_pass_gate,
+                                    int64_t* chord, double* t_hit, double* time, int32_t* obb, void* stream);
 
 /* ---- batch planner building blocks (device pointers) ------------------------------- */
 /* Replace OMPL's sampler / nearest-neighbour structure behind PathPlanner::planPath

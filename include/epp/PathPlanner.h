@@ -142,6 +142,17 @@ public:
     void candidateClearances(const std::vector<std::vector<Vec3>>& waypointSets, double v_max, double a_max, double dt,
                              std::vector<double>& clearance, std::vector<long>* row = nullptr,
                              std::vector<double>* time = nullptr, std::vector<int>* nearest = nullptr) const;
+    // Where and against what each of K candidate waypoint sets' trajectories first fails the
+    // swept check (an addition of this build): the fit of every set as above and, on the same
+    // stream with one synchronisation, epp_traj_first_hit_batch (include/epp.h) of the fits'
+    // chords at dt.  chord[k]: sweepCandidateTrajectories' firstInvalidChord; t[k]: the
+    // parameter in [0, 1] along that chord at which it enters the blocking OBB (0: its start
+    // row is in collision); time / obb (optional): the track time of that point and the OBB's
+    // index in the world's order (the lowest among equals).  -1, +inf, -1.0, -1 for a set
+    // without a failing chord.  Throws as checkCandidateTrajectories.
+    void candidateFirstHits(const std::vector<std::vector<Vec3>>& waypointSets, double v_max, double a_max, double dt,
+                            bool canPassGate, std::vector<long>& chord, std::vector<double>& t,
+                            std::vector<double>* time = nullptr, std::vector<int>* obb = nullptr) const;
     std::vector<Vec3> includeGates2(std::vector<std::vector<Vec3>> waypoints) const;
     // planPaths of consecutive gate-to-gate segments, then includeGates2 of their paths (an
     // addition of this build, for OnlineTrajGenerator::preComputeTraj): the same answers as

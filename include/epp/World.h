@@ -56,6 +56,14 @@ public:
     // on one; nearest[i] (optional) that OBB's index in obbs(), the lowest among equals.
     // +inf / -1 without a collision OBB (an empty world included) or for a non-finite point.
     void clearance(const double* xyz, int64_t n, double* dist, int32_t* nearest = nullptr) const;
+    // First hit (an addition of this build; epp_motions_first_hit, include/epp.h): t[i] is the
+    // parameter in [0, 1] at which the edge s1[i] -> s2[i] first enters an OBB that
+    // checkRayValid(s1[i], s2[i], canPassGate) would reject it for, 0 for a start in collision;
+    // obb[i] (optional) that OBB's index in obbs(), the lowest among equals.  +inf / -1 for a
+    // valid edge (an empty world included).  What MotionValidator::checkMotion(s1, s2,
+    // lastValid) needs.
+    void firstHits(const double* s1, const double* s2, int64_t n, bool canPassGate, double* t,
+                   int32_t* obb = nullptr) const;
 
     // Device handle (rebuilt lazily after mutations); nullptr for an empty world.
     const epp_world* device() const;
