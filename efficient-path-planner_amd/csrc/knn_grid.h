@@ -1,4 +1,4 @@
-// knn_grid.h — the uniform grid of the exact k-NN, shared by knn.hip's kernels and the
+// knn_grid.h — the uniform grid of the exact k-NN, shared by the k-NN kernels (knn_kernels.h) and the
 // batched planner's (plan_batch.hip): the grid parameters and their shape (KnnGrid,
 // knn_grid_shape, knn_cell_axis), the workspace layout (KnnLayout), the cell-count scan
 // (knn_scan_block) and the per-query pieces: sorted top-K insert, the exact stopping rule,

@@ -8,7 +8,7 @@
 //   k_mask_edges[_count]        : drops the edges the motion check refused (and counts the rest)
 //   k_rev_count / scan / fill / sort : the reverse edges of a k-NN table as a CSR
 //
-// The k-NN itself is knn.hip, the batched planner plan_batch.hip; both use the host helpers
+// The k-NN itself is knn*.hip (knn_kernels.h), the batched planner plan_batch.hip; both use the host helpers
 // defined here (planner_common.h).  States and edges are checked by states.hip and
 // motions.hip; the host runs the shortest-path search over the valid edges.
 #include <hip/hip_runtime.h>

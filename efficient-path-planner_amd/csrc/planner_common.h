@@ -1,4 +1,4 @@
-// planner_common.h — what the planner's device files (planner.hip, knn.hip via knn_grid.h,
+// planner_common.h — what the planner's device files (planner.hip, knn*.hip via knn_grid.h,
 // plan_batch.hip) share: the uniform sampler, the decoupled look-back of the single-pass
 // ordered scans, the ordered compaction's chunk shape, and the host helpers planner.hip
 // defines for all three.

@@ -5,8 +5,9 @@ Walks the gfx950 bundles of both libraries' .hip_fatbin (as tests/test_kernel_re
 does).  Per kernel: its disassembly (llvm-objdump; no addresses, no raw bytes, branch
 targets as offsets from the kernel's start) and its metadata note (VGPRs, SGPRs, LDS bytes,
 private segment, kernarg size).  Prints three lists: kernels only in A, kernels only in B,
-and kernels whose text or metadata differ, with a unified diff for each.  Exit status 0 when
-all three are empty, 1 otherwise.  It only compares.
+and kernels whose text or metadata differ, with a unified diff for each.  A kernel whose
+parameter list changed (and with it its mangled name) is listed first and then compared with
+its other self.  Exit status 0 when all lists are empty, 1 otherwise.  It only compares.
 """
 import difflib
 import os
@@ -96,13 +97,27 @@ def kernels(lib_path):
     return out
 
 
+def _base(name):
+    """The demangled name without its parameter list: epp::k_knn_tile<16>."""
+    out = subprocess.run(["c++filt", name], check=True, capture_output=True, text=True).stdout  # (binutils)
+    return out.replace("(anonymous namespace)::", "").split("(")[0].split()[-1]
+
+
 def main():
     if len(sys.argv) != 3:
         sys.exit(__doc__)
     a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
+    print(f"A = {sys.argv[1]}: {len(a)} kernels\nB = {sys.argv[2]}: {len(b)} kernels")
+    # a kernel template's mangled name holds its parameter types: one whose signature changed is
+    # paired by its name without them and compared under A's name
+    by_base = {_base(k): k for k in set(b) - set(a)}
+    resigned = {k: by_base[_base(k)] for k in sorted(set(a) - set(b)) if _base(k) in by_base}
+    print(f"\n== signature changed (compared below as one kernel): {len(resigned)}")
+    for ka, kb in resigned.items():
+        print(f"  {ka}\n    -> {kb}")
+        b[ka] = b.pop(kb)
     only_a, only_b = sorted(set(a) - set(b)), sorted(set(b) - set(a))
     differ = [k for k in sorted(set(a) & set(b)) if a[k] != b[k]]
-    print(f"A = {sys.argv[1]}: {len(a)} kernels\nB = {sys.argv[2]}: {len(b)} kernels")
     for title, names in (("only in A", only_a), ("only in B", only_b), ("different", differ)):
         print(f"\n== {title}: {len(names)}")
         for k in names:
@@ -115,7 +130,7 @@ def main():
                 print(f"    .{m}: {ma[m]} -> {mb[m]}")
         print(f"    instructions: {len(ta)} -> {len(tb)}")
         sys.stdout.writelines(l + "\n" for l in difflib.unified_diff(ta, tb, "A", "B", lineterm="", n=2))
-    return 1 if only_a or only_b or differ else 0
+    return 1 if resigned or only_a or only_b or differ else 0
 
 
 if __name__ == "__main__":

@@ -24,7 +24,7 @@ import pytest
 from eppamd import capi
 
 LLVM = "/opt/rocm/lib/llvm/bin"
-HOT = re.compile(r"k_knn_tile|k_knn_wave|k_knn_retry|k_states_v5|k_states_small|k_motions_v5|k_motions_small|"
+HOT = re.compile(r"k_knn_tile|k_knn_retry|k_states_v5|k_states_small|k_motions_v5|k_motions_small|"
                  r"k_pb_|k_minsnap|k_refit|k_check_refit|k_compact|k_rev_|k_traj_|k_sample_")
 # k_motions_v5<W, MODE, IDX>: (W, MODE) pairs that spill at 128 VGPRs
 KNOWN_SPILLS = {(2, 1), (4, 1), (8, 1), (16, 0), (16, 1), (32, 0), (32, 1)}
