@@ -131,6 +131,10 @@ def lib() -> C.CDLL:
             "epp_mask_edges": (i32, [vp, vp, i64, vp]),
             "epp_mask_edges_count": (i32, [vp, vp, i64, i32, vp, vp]),
             "epp_check_knn_motions": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp]),
+            # debug entries (csrc/host_dbg_planner.cpp; not in include/epp.h)
+            "epp_dbg_plan_batch": (i32, [vp, i32, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32,
+                                         vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, i32, vp, vp]),
+            "epp_dbg_reverse_csr": (i32, [vp, i32, i32, vp, vp, vp]),
         }
         for name, (res, args) in sig.items():
             if os.environ.get("EPP_LIB") and not hasattr(l, name):
@@ -715,6 +719,65 @@ def knn_edges(nodes: np.ndarray, nbr: np.ndarray):
     check(lib().epp_knn_edges(d_n.ptr, d_k.ptr, n, k, d_1.ptr, d_2.ptr, None))
     sync()
     return d_1.download(np.float64, 3 * n * k).reshape(-1, 3), d_2.download(np.float64, 3 * n * k).reshape(-1, 3)
+
+
+def dbg_plan_batch(world: "World", can_pass_gate, lo, hi, ns: int, k: int, segs, seqs=(1,), fill: int = 0) -> dict:
+    """epp_dbg_plan_batch: one batch through the batched planner's device stages
+    (plan_batch_layout / plan_batch_launch), no solver and no fallback.  segs: per problem a
+    dict with the caller-filled fields of PlanSeg (seed, s, g, bound, gbound, glo, ghi, h,
+    cap).  The batch runs once per entry of seqs on one workspace; fill bit 0: the workspace
+    and the pinned block hold 0xFF bytes before the first run, bit 1: the emitted part of
+    the pinned block is overwritten with 0xFF between runs.  Returns the last run's emitted
+    block: hdr (u64, 3 + 6 S), slots (u32), rows (u16, rows x k), need (doubles, slots x 3),
+    row_off / need_off / need_cap per problem, done (the completion slots), nodes (per
+    problem its node list from the device) and the layout's sizes."""
+    S = len(segs)
+    lo = np.ascontiguousarray(lo, np.float64)
+    hi = np.ascontiguousarray(hi, np.float64)
+    seeds = np.ascontiguousarray([int(q["seed"]) & 0xFFFFFFFFFFFFFFFF for q in segs], np.uint64)
+    ends = np.ascontiguousarray([np.concatenate([q["s"], q["g"]]) for q in segs], np.float64)
+    bounds = np.ascontiguousarray([[q["bound"], q["gbound"]] for q in segs], np.float64)
+    gbox = np.ascontiguousarray([np.concatenate([q["glo"], q["ghi"]]) for q in segs], np.float64)
+    h = np.ascontiguousarray([q["h"] for q in segs], np.float64)
+    cap = np.ascontiguousarray([q["cap"] for q in segs], np.int32)
+    seqs = np.ascontiguousarray(seqs, np.uint32)
+    slots_cap = int(np.maximum(cap, 0).sum()) + 4
+    need_slots = S * (ns + 4)
+    hdr = np.zeros(3 + 6 * S, np.uint64)
+    slots = np.zeros(slots_cap, np.uint32)
+    rows = np.zeros((slots_cap, k), np.uint16)
+    need = np.zeros((need_slots, 3))
+    row_off, need_off = np.zeros(S, np.int64), np.zeros(S, np.int64)
+    need_cap = np.zeros(S, np.int32)
+    done = np.zeros(1024, np.uint32)
+    nodes = np.zeros((S, ns + 2, 3))
+    meta = np.zeros(6, np.int64)
+    check(lib().epp_dbg_plan_batch(world.handle, 1 if can_pass_gate else 0, _ptr(lo), _ptr(hi), int(ns), int(k), S,
+                                   _ptr(seeds), _ptr(ends), _ptr(bounds), _ptr(gbox), _ptr(h), _ptr(cap),
+                                   _ptr(seqs), len(seqs), int(fill), _ptr(hdr), _ptr(slots), _ptr(rows), slots_cap,
+                                   _ptr(need), need_slots, _ptr(row_off), _ptr(need_off), _ptr(need_cap),
+                                   _ptr(done), len(done), _ptr(nodes), _ptr(meta)))
+    n_nodes = hdr[3 + 3 * S:3 + 4 * S].astype(np.int64)
+    return dict(hdr=hdr, slots=slots, rows=rows, need=need, row_off=row_off, need_off=need_off, need_cap=need_cap,
+                done=done[:int(meta[2])].copy(), seq=int(seqs[-1]),
+                nodes=[nodes[p, :max(0, min(int(n_nodes[p]), ns + 2))].copy() for p in range(S)],
+                cap_total=int(meta[0]), need_total=int(meta[1]), ns_log=int(meta[3]), dev_bytes=int(meta[4]),
+                host_bytes=int(meta[5]))
+
+
+def dbg_reverse_csr(nbr: np.ndarray):
+    """epp_dbg_reverse_csr: the reverse edges of the masked k-NN table nbr (n x k, -1: none) as
+    a CSR built on the device: (roff (n + 1), radj (roff[n] sources, every node's ascending),
+    radj16 -- the same as u16 -- or None for n > 65535)."""
+    nbr = np.ascontiguousarray(nbr, np.int32)
+    n, k = nbr.shape
+    d_n = DeviceBuffer.from_array(nbr)
+    roff = np.zeros(n + 1, np.int32)
+    radj = np.zeros(n * k, np.int32)
+    radj16 = np.zeros(n * k, np.uint16) if n <= 65535 else None
+    check(lib().epp_dbg_reverse_csr(d_n.ptr, n, k, _ptr(roff), _ptr(radj), _ptr(radj16) if radj16 is not None else None))
+    ne = int(roff[n])
+    return roff, radj[:ne].copy(), (radj16[:ne].copy() if radj16 is not None else None)
 
 
 class Comm:

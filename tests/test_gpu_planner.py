@@ -21,6 +21,7 @@ import oracle as O
 from eppamd import capi, config, synth
 
 from conftest import CONFIG, ROOT
+from knn_ref import knn_ref as _knn_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -50,19 +51,6 @@ def test_sample_uniform_bit_exact(start):
     assert np.array_equal(got, ref)
     if start == 0:
         assert np.array_equal(got, O.sample_states(0xC0FFEE, lo, hi, n))
-
-
-def _knn_ref(nodes, k, max_dist=0.0):
-    n = len(nodes)
-    out = np.full((n, k), -1, np.int32)
-    r2 = max_dist * max_dist if max_dist > 0 else 1e300
-    for i in range(n):
-        d = nodes - nodes[i]
-        d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
-        cand = np.nonzero((d2 < r2) & (np.arange(n) != i))[0]
-        order = cand[np.lexsort((cand, d2[cand]))][:k]  # distance, then lower index
-        out[i, :len(order)] = order
-    return out
 
 
 @pytest.mark.parametrize("method", ["brute", "grid"])
