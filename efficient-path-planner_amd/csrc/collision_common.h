@@ -1,5 +1,6 @@
-// collision_common.h — device helpers shared by the OBB validity kernels (states.hip,
-// motions.hip) and their host-side launch helpers.
+// collision_common.h — device helpers shared by the OBB kernels (states.hip, the motions_*.hip
+// kernel files, small.hip, clearance.hip, first_hit.hip, trajcheck.hip, minsnap.hip) and the
+// allow_lds launch helper; the other host-side launch helpers are in launch_helpers.h.
 //
 // All decision arithmetic is IEEE fp64 with contraction disabled (-ffp-contract=off), in
 // the reference's evaluation order, so the booleans match the reference bit for bit:
@@ -17,6 +18,7 @@
 #include <string>
 
 #include "epp_internal.h"
+#include "launch_helpers.h"
 
 namespace epp {
 SmallWorld small_world(const epp_world* w);
@@ -37,9 +39,6 @@ epp_status launch_motions_small(const SmallWorld& sw, int32_t mode, const double
                                 uint32_t seq = 0);
 
 namespace {
-
-constexpr int kBlock = 256;
-constexpr uint32_t kLdsBudget = 150 * 1024;
 
 struct Acc {
     const double* f;
@@ -501,14 +500,6 @@ __device__ __forceinline__ bool states_exact_pt(const unsigned char* sbase, uint
     return hit;
 }
 
-// ---- k_motions_v2: motion checks out of LDS ----------------------------------------
-// The coarse grid (occupancy masks, cell starts, cell lists) and the AoS OBB records are
-// staged into LDS once per persistent workgroup; one edge per lane per iteration.  Every
-// candidate test is branch-free on LDS data: all record fields are read up front, so a
-// candidate costs one LDS round trip instead of the short-circuit chain of dependent
-// global loads of k_motions.  Same candidate order, de-duplication (first common cell)
-// and predicates as ray_valid / ray_valid_d32 (src/World.cpp:130-162, src/OBB.cpp:10-91).
-
 // OBB::checkCollisionWithRay (src/OBB.cpp:10-61) on one AoS record, branch-free.  `r` is
 // the owner's inflation radius; the endpoint tests inflate only collision OBBs (:13-14),
 // the slab test always (:28).  Axes are processed in order with the reference's min /
@@ -593,43 +584,6 @@ __device__ __forceinline__ RayParts rec_ray_parts(const double* rec, const doubl
     return p;
 }
 
-struct DevInfo {
-    int cus = 256;
-    bool init = false;
-};
-DevInfo g_dev[64];
-
-int cu_count() {
-    int d = 0;
-    (void)hipGetDevice(&d);
-    if (d < 0 || d >= 64) return 256;
-    if (!g_dev[d].init) {
-        int c = 0;
-        if (hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, d) == hipSuccess && c > 0)
-            g_dev[d].cus = c;
-        g_dev[d].init = true;
-    }
-    return g_dev[d].cus;
-}
-
-// integer environment variable (test hooks only)
-int env_int(const char* name, int dflt) {
-    const char* v = std::getenv(name);
-    return v && *v ? std::atoi(v) : dflt;
-}
-
-// Persistent grid: at most `per_cu` resident 256-thread blocks per CU (LDS permitting),
-// each looping over item groups, so the world is staged into LDS once per block.
-int grid_for(int64_t groups, uint32_t lds_bytes) {
-    const int64_t need = (groups + kBlock - 1) / kBlock;
-    int per_cu = 4;
-    if (lds_bytes > 0)
-        per_cu = std::max(1, std::min<int>(per_cu, (int)((160u * 1024u) / lds_bytes)));
-    const int64_t cap = (int64_t)cu_count() * per_cu;
-    int64_t g = need < cap ? need : cap;
-    return (int)(g < 1 ? 1 : g);
-}
-
 // Opt a kernel in to more than 64 KB of dynamic LDS (static LDS counts against the same
 // 160 KB).  A failure here must not linger as the thread's last HIP error.
 template <typename K>
@@ -645,16 +599,6 @@ void allow_lds(K kernel, uint32_t static_bytes = 0) {
             (void)hipGetLastError();
     }
 }
-
-epp_status launch_error(const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error(std::string(what) + ": " + hipGetErrorString(e));
-        return EPP_ERR_HIP;
-    }
-    return EPP_OK;
-}
-
 
 }  // namespace
 }  // namespace epp

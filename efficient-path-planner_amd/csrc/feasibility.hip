@@ -31,6 +31,7 @@
 #include <string>
 
 #include "epp_internal.h"
+#include "launch_helpers.h"
 
 namespace epp {
 namespace {
@@ -291,15 +292,6 @@ __global__ __launch_bounds__(kFeasBlock) void k_traj_scale(double* seg_times, do
     }
 }
 
-epp_status feas_launch_error(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error(std::string(what) + ": " + hipGetErrorString(e));
-        return EPP_ERR_HIP;
-    }
-    return EPP_OK;
-}
-
 }  // namespace
 }  // namespace epp
 
@@ -316,7 +308,7 @@ epp_status epp_traj_peaks(const double* seg_times, const double* coeffs, const i
     if (n_tracks == 0) return EPP_OK;
     hipLaunchKernelGGL(k_traj_peaks, dim3(n_tracks), dim3(kFeasBlock), 0, (hipStream_t)stream, seg_times, coeffs,
                        wp_offsets, n_tracks, peaks, status);
-    return feas_launch_error("epp_traj_peaks");
+    return launch_error("epp_traj_peaks");
 }
 
 epp_status epp_traj_scale_to_limits(double* seg_times, double* coeffs, const int32_t* wp_offsets, int32_t n_tracks,
@@ -332,7 +324,7 @@ epp_status epp_traj_scale_to_limits(double* seg_times, double* coeffs, const int
     if (n_tracks == 0) return EPP_OK;
     hipLaunchKernelGGL(k_traj_scale, dim3(n_tracks), dim3(kFeasBlock), 0, (hipStream_t)stream, seg_times, coeffs,
                        wp_offsets, n_tracks, v_max, a_max, scale, status);
-    return feas_launch_error("epp_traj_scale_to_limits");
+    return launch_error("epp_traj_scale_to_limits");
 }
 
 }  // extern "C"

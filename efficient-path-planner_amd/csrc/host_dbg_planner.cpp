@@ -14,10 +14,8 @@
 #include <vector>
 
 #include "epp_internal.h"
+#include "launch_helpers.h"
 
-namespace epp {
-epp_status last(const char* what);  // (planner.hip: hipGetLastError as a status)
-}
 using namespace epp;
 
 namespace {
@@ -46,7 +44,7 @@ epp_status fail(epp_status st, const char* msg) {
     return st;
 }
 epp_status hip_fail(const char* what) {  // a HIP call failed: its error as a status
-    const epp_status st = last(what);
+    const epp_status st = launch_error(what);
     return st != EPP_OK ? st : fail(EPP_ERR_HIP, what);
 }
 }  // namespace

@@ -50,13 +50,13 @@ epp_status knn_grid_launch(const double* nodes, int n, int k, double max_dist, i
     const char* tile_env = std::getenv("EPP_KNN_TILE");
     const bool tiled = !(tile_env && *tile_env) || std::atoi(tile_env) != 0;
     if (tiled && (k == 4 || k == 8 || k == 16)) {
-        const int cus = cu_count_planner();
+        const int cus = cu_count();
         knn_tile_launch(k, cus, nodes, r2, w, nbr, s);
         knn_retry_launch(k, cus, nodes, r2, w, nbr, s);
     } else {
         knn_walk_launch(k, n, r2, w, nbr, s);
     }
-    return last("epp_knn_grid");
+    return launch_error("epp_knn_grid");
 }
 
 CachedWs g_knn_ws[64];
@@ -73,7 +73,7 @@ epp_status epp_knn_bruteforce(const double* nodes, int32_t n, int32_t k, double 
     if (!knn_args_ok("epp_knn", nodes, n, k, nbr)) return EPP_ERR_INVALID_ARGUMENT;
     if (n == 0) return EPP_OK;
     knn_brute_launch(k, nodes, n, knn_r2max(max_dist), nbr, (hipStream_t)stream);
-    return last("epp_knn_bruteforce");
+    return launch_error("epp_knn_bruteforce");
 }
 
 epp_status epp_knn(const double* nodes, int32_t n, int32_t k, double max_dist, int32_t* nbr, void* stream) {

@@ -73,7 +73,7 @@ inline KnnWs knn_ws_parts(char* buf, const KnnLayout& L) {
     return w;
 }
 
-// Each enqueues its kernels on s and returns; the caller reads the launch status (last()).
+// Each enqueues its kernels on s and returns; the caller reads the launch status (launch_error()).
 // (knn_build.hip) the grid over box_lo .. box_hi (the caller's box: shape on the host) or, with
 // none, over the nodes' bounding box (measured on the device); the cell-sorted copy of the nodes
 void knn_build_launch(const double* nodes, int n, const KnnWs& w, hipStream_t s, const double* box_lo,

@@ -901,7 +901,7 @@ epp_status epp::plan_batch_launch(const epp_world* world, int32_t can_pass_gate,
     } else {
         if (hipMemcpyAsync(d + L.o_seg, h + L.h_seg, (size_t)L.S * sizeof(PlanSeg), hipMemcpyHostToDevice, s) !=
             hipSuccess)
-            return last("plan_batch_launch");
+            return launch_error("plan_batch_launch");
     }
     const int64_t clr = std::max<int64_t>({L.ns, R ? L.NS >> 4 : 0, R ? (int64_t)P.nclr : 0, (int64_t)L.nbc, (int64_t)L.nctr});
     pb_mark(s, "begin");
@@ -925,7 +925,7 @@ epp_status epp::plan_batch_launch(const epp_world* world, int32_t can_pass_gate,
             const int v = e && *e ? std::atoi(e) : 28;
             return std::max(1, std::min(64, v));
         }();
-        const dim3 gr((unsigned)std::max(1, cu_count_planner() * rows_wg)), br(64);
+        const dim3 gr((unsigned)std::max(1, cu_count() * rows_wg)), br(64);
         if (L.k == 4) hipLaunchKernelGGL(k_pb_rows<4>, gr, br, 0, s, P);
         else if (L.k == 8) hipLaunchKernelGGL(k_pb_rows<8>, gr, br, 0, s, P);
         else hipLaunchKernelGGL(k_pb_rows<16>, gr, br, 0, s, P);
@@ -952,5 +952,5 @@ epp_status epp::plan_batch_launch(const epp_world* world, int32_t can_pass_gate,
                        reinterpret_cast<uint4*>(h + L.h_rows), reinterpret_cast<uint4*>(h + L.h_need),
                        reinterpret_cast<uint32_t*>(h + L.h_done), seq);
     pb_mark(s, "emit");
-    return last("plan_batch_launch");
+    return launch_error("plan_batch_launch");
 }

@@ -8,8 +8,8 @@
 //   k_mask_edges[_count]        : drops the edges the motion check refused (and counts the rest)
 //   k_rev_count / scan / fill / sort : the reverse edges of a k-NN table as a CSR
 //
-// The k-NN itself is knn*.hip (knn_kernels.h), the batched planner plan_batch.hip; both use the host helpers
-// defined here (planner_common.h).  States and edges are checked by states.hip and
+// The k-NN itself is knn*.hip (knn_kernels.h), the batched planner plan_batch.hip; both use the scan tag
+// handed out here (planner_common.h).  States and edges are checked by states.hip and
 // motions.hip; the host runs the shortest-path search over the valid edges.
 #include <hip/hip_runtime.h>
 
@@ -32,21 +32,6 @@ uint32_t next_scan_tag() {
     do t = (g_scan_tag.fetch_add(1, std::memory_order_relaxed) + 1u) & 0xffffffu;
     while (t == 0u);
     return t;
-}
-
-int cu_count_planner() {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    return cus;
-}
-
-epp_status last(const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error(std::string(what) + ": " + hipGetErrorString(e));
-        return EPP_ERR_HIP;
-    }
-    return EPP_OK;
 }
 
 namespace {
@@ -279,7 +264,7 @@ epp_status epp_sample_uniform(uint64_t seed, const double lo[3], const double hi
     if (n == 0) return EPP_OK;
     hipLaunchKernelGGL(k_sample_uniform, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        seed, lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], n, start, xyz, nullptr, (int64_t)0);
-    return last("epp_sample_uniform");
+    return launch_error("epp_sample_uniform");
 }
 
 epp_status epp_compact_states(const double* xyz, const uint8_t* valid, int64_t n, double* out, int64_t* n_out,
@@ -318,10 +303,10 @@ epp_status epp_compact_states_ws(const double* xyz, const uint8_t* valid, int64_
     const int nb = (int)std::max<int64_t>(1, (n + kCompactChunk - 1) / kCompactChunk);
     // the workspace may hold anything (e.g. carved from a buffer that held other data):
     // zero its status words first, so none reads as published in this launch
-    if (hipMemsetAsync(ws, 0, (size_t)nb * 8, (hipStream_t)stream) != hipSuccess) return last("epp_compact_states");
+    if (hipMemsetAsync(ws, 0, (size_t)nb * 8, (hipStream_t)stream) != hipSuccess) return launch_error("epp_compact_states");
     hipLaunchKernelGGL(k_compact, dim3(nb), dim3(kCompactThreads), 0, (hipStream_t)stream, xyz, valid, n,
                        static_cast<unsigned long long*>(ws), next_scan_tag(), out, n_out);
-    return last("epp_compact_states");
+    return launch_error("epp_compact_states");
 }
 
 epp_status epp_mask_edges(int32_t* nbr, const uint8_t* valid, int64_t m, void* stream) {
@@ -332,7 +317,7 @@ epp_status epp_mask_edges(int32_t* nbr, const uint8_t* valid, int64_t m, void* s
     if (m == 0) return EPP_OK;
     hipLaunchKernelGGL(k_mask_edges, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, (hipStream_t)stream, nbr,
                        valid, m);
-    return last("epp_mask_edges");
+    return launch_error("epp_mask_edges");
 }
 
 epp_status epp_mask_edges_count(int32_t* nbr, const uint8_t* valid, int64_t m, int32_t target, int64_t* count,
@@ -341,7 +326,7 @@ epp_status epp_mask_edges_count(int32_t* nbr, const uint8_t* valid, int64_t m, i
         set_error("epp_mask_edges_count: invalid argument");
         return EPP_ERR_INVALID_ARGUMENT;
     }
-    if (hipMemsetAsync(count, 0, 2 * sizeof(int64_t), (hipStream_t)stream) != hipSuccess) return last("epp_mask_edges_count");
+    if (hipMemsetAsync(count, 0, 2 * sizeof(int64_t), (hipStream_t)stream) != hipSuccess) return launch_error("epp_mask_edges_count");
     return epp::mask_edges_count_acc(nbr, valid, m, target, count, stream);
 }
 
@@ -358,7 +343,7 @@ epp_status epp::mask_edges_count_acc(int32_t* nbr, const uint8_t* valid, int64_t
     const int64_t blocks = std::min<int64_t>((m + kMaskThreads - 1) / kMaskThreads, 256);
     hipLaunchKernelGGL(k_mask_edges_count, dim3((unsigned)blocks), dim3(kMaskThreads), 0, s, nbr, valid, m, target,
                        reinterpret_cast<unsigned long long*>(count), out16);
-    return last("epp_mask_edges_count");
+    return launch_error("epp_mask_edges_count");
 }
 
 extern "C" {
@@ -373,7 +358,7 @@ epp_status epp_knn_edges(const double* nodes, const int32_t* nbr, int32_t n, int
     if (m == 0) return EPP_OK;
     hipLaunchKernelGGL(k_knn_edges, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, (hipStream_t)stream, nodes,
                        nbr, m, k, s1, s2);
-    return last("epp_knn_edges");
+    return launch_error("epp_knn_edges");
 }
 
 }  // extern "C"
@@ -386,10 +371,10 @@ epp_status epp::reverse_csr(const int32_t* nbr, int32_t n, int32_t k, int32_t* c
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t m = (int64_t)n * k;
-    if (hipMemsetAsync(cnt, 0, (size_t)n * 4, s) != hipSuccess) return last("reverse_csr");
+    if (hipMemsetAsync(cnt, 0, (size_t)n * 4, s) != hipSuccess) return launch_error("reverse_csr");
     hipLaunchKernelGGL(k_rev_count, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, nbr, m, cnt);
     hipLaunchKernelGGL(k_rev_scan, dim3(1), dim3(1024), 0, s, cnt, n, roff, fill);
     hipLaunchKernelGGL(k_rev_fill, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, nbr, m, k, fill, radj);
     hipLaunchKernelGGL(k_rev_sort, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, roff, n, radj, radj16);
-    return last("reverse_csr");
+    return launch_error("reverse_csr");
 }

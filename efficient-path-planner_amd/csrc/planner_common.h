@@ -1,20 +1,19 @@
 // planner_common.h — what the planner's device files (planner.hip, knn*.hip via knn_grid.h,
 // plan_batch.hip) share: the uniform sampler, the decoupled look-back of the single-pass
-// ordered scans, the ordered compaction's chunk shape, and the host helpers planner.hip
-// defines for all three.
+// ordered scans, the ordered compaction's chunk shape, and the scan tag planner.hip
+// hands out for all three.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "epp_internal.h"
+#include "launch_helpers.h"  // cu_count, launch_error
 
 namespace epp {
 
 // (planner.hip)
 uint32_t next_scan_tag();  // a launch tag for lb_publish / lb_exclusive: 24 bits, never 0
-int cu_count_planner();    // the current device's CU count
-epp_status last(const char* what);  // hipGetLastError as a status (sets the error text)
 
 namespace {
 

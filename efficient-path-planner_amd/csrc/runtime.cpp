@@ -1,17 +1,61 @@
 // runtime.cpp — error state and thin HIP runtime wrappers of the C ABI (include/epp.h).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <string>
 
 #include "epp_internal.h"
+#include "launch_helpers.h"
 
 namespace epp {
 namespace {
 thread_local std::string g_last_error;
 }
 void set_error(const std::string& msg) { g_last_error = msg; }
+
+// ---- launch helpers (launch_helpers.h) ---------------------------------------------------
+namespace {
+std::atomic<int> g_cus[64];  // per device, 0: not asked yet (the planner's threads ask too)
+}  // namespace
+
+int cu_count() {
+    int d = 0;
+    (void)hipGetDevice(&d);
+    if (d < 0 || d >= 64) return 256;
+    int c = g_cus[d].load(std::memory_order_relaxed);
+    if (c == 0) {
+        if (hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || c <= 0) c = 256;
+        g_cus[d].store(c, std::memory_order_relaxed);
+    }
+    return c;
+}
+
+int env_int(const char* name, int dflt) {
+    const char* v = std::getenv(name);
+    return v && *v ? std::atoi(v) : dflt;
+}
+
+int grid_for(int64_t groups, uint32_t lds_bytes) {
+    const int64_t need = (groups + kBlock - 1) / kBlock;
+    int per_cu = 4;
+    if (lds_bytes > 0)
+        per_cu = std::max(1, std::min<int>(per_cu, (int)((160u * 1024u) / lds_bytes)));
+    const int64_t cap = (int64_t)cu_count() * per_cu;
+    int64_t g = need < cap ? need : cap;
+    return (int)(g < 1 ? 1 : g);
+}
+
+epp_status launch_error(const char* what) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        set_error(std::string(what) + ": " + hipGetErrorString(e));
+        return EPP_ERR_HIP;
+    }
+    return EPP_OK;
+}
 }  // namespace epp
 
 #define EPP_HIP_RET(call)                                                            \

@@ -20,7 +20,6 @@ if not os.path.exists(lib_path):
                     f"BUILD={out}/build_mtl", f"LIB={lib_path}", "EXTRA=-DEPP_MOTIONS_TL", lib_path], check=True)
 capi.LIB_PATH = lib_path
 L = capi.lib()
-L.epp_dbg_motions_tl.argtypes = [C.c_void_p, C.c_int64]
 cfg = config.load(os.path.join(ROOT, "configs", "config.json"))
 geom = config.geometry(cfg)
 rg, ro = config.inflate_radii(cfg)
@@ -33,6 +32,9 @@ dv = capi.DeviceBuffer(N)
 kernel = sys.argv[1] if len(sys.argv) > 1 else "v5"
 if kernel == "v4":
     os.environ["EPP_MOTIONS_KERNEL"] = "v4"
+# each kernel file keeps its own timeline: the cell-list kernels' (v4) or the tile kernel's (v5)
+read_tl = L.epp_dbg_motions_cells_tl if kernel == "v4" else L.epp_dbg_motions_tile_tl
+read_tl.argtypes = [C.c_void_p, C.c_int64]
 names = (("walk cycles", "flush cycles", "total cycles", "entries", "queued", "cell pairs") if kernel == "v4" else
          ("filter+queue", "flush cycles", "total cycles", "cand loop", "pairs", "staging"))
 for mode in (0, 1):
@@ -41,7 +43,7 @@ for mode in (0, 1):
     capi.sync()
     waves = N // 64
     tl = np.zeros((waves, 6), np.uint64)
-    capi.check(L.epp_dbg_motions_tl(tl.ctypes.data, waves))
+    capi.check(read_tl(tl.ctypes.data, waves))
     tl = tl.astype(np.int64)
     live = tl[:, 2] > 0
     tl = tl[live]
