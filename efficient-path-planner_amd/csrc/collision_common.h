@@ -1,12 +1,13 @@
-// collision_common.h — device helpers shared by the OBB kernels (states.hip, the motions_*.hip
-// kernel files, small.hip, clearance.hip, first_hit.hip, trajcheck.hip, minsnap.hip) and the
-// allow_lds launch helper; the other host-side launch helpers are in launch_helpers.h.
+// collision_common.h — device helpers shared by the OBB kernels (the states_*.hip and
+// motions_*.hip kernel files, small.hip, clearance.hip, first_hit.hip, trajcheck.hip,
+// minsnap.hip) and the allow_lds launch helper; the other host-side launch helpers are in
+// launch_helpers.h.  What only the state kernels use is in states_kernels.h and states_*.hip.
 //
 // All decision arithmetic is IEEE fp64 with contraction disabled (-ffp-contract=off), in
 // the reference's evaluation order, so the booleans match the reference bit for bit:
 //   OBB::checkCollisionWithPoint  src/OBB.cpp:63-91   (obb_point_hit, rec_hit)
 //   OBB::checkCollisionWithRay    src/OBB.cpp:10-61   (obb_ray_hit, rec_ray_hit)
-//   World::checkPointValidity     src/World.cpp:80-128 (point_valid, states_exact_rec)
+//   World::checkPointValidity     src/World.cpp:80-128 (point_valid; states_kernels.h: states_exact_rec)
 //   World::checkRayValid          src/World.cpp:130-162 (ray_valid)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -267,25 +268,6 @@ __device__ __forceinline__ void store4(uint8_t* __restrict__ out, int64_t first,
     }
 }
 
-// ---- k_states: wave-cooperative candidate testing ----------------------------------
-// Phase 1 (per lane, 4 states): bounds + fine-mask test.  A state whose sub-cell is
-// occupied owns a segment of (state, candidate OBB) pairs: its coarse cell's list.
-// Phase 2 (per wave): the segments are compacted into LDS (wave prefix sums) and the 64
-// lanes take one pair each (a binary search over the segment offsets finds the pair's
-// state), setting per-state "hit" bits with LDS atomics.  Only ~6% of uniform samples
-// have candidates; without this a wavefront would run its slowest lane's candidate loop
-// for every state slot.
-constexpr int kSegCap = 96;     // needy states a wave handles cooperatively per group
-constexpr int kPairCap = 512;   // (state, candidate) pairs a wave handles cooperatively
-struct WaveScratch {
-    double xyz[kSegCap][3];        // coordinates of the needy states
-    uint32_t seg_start[kSegCap];   // exclusive prefix of pair counts
-    uint32_t seg_state[kSegCap];   // sid (8 bits) | first candidate entry << 8
-    uint8_t head[kPairCap];        // segment index at its first pair, 0 elsewhere
-    uint32_t bits[8];              // hit bits of the 256 states of the wave's group
-};
-constexpr uint32_t kScratchBytes = (kBlock / 64) * ((sizeof(WaveScratch) + 15) & ~15u);
-
 __device__ __forceinline__ void wave_lds_sync() {
     // LDS operations of one wavefront complete in order; this only stops the compiler
     // from moving memory accesses across the point (no vmcnt drain: the prefetched
@@ -442,61 +424,6 @@ __device__ __forceinline__ bool d32_pair_hit(const double* rec, const double ps[
         const double qz = ps[2] + (pe[2] - ps[2]) * t;
         hit = rec_hit<false>(rr, rg, ro, qx, qy, qz, cp, 0.0);
     }
-    return hit;
-}
-
-// Exact test on the AoS records + the cell's candidate list (no early exit: the lists
-// are short and straight-line control flow keeps the wave converged).  `sbase` points
-// at the records (LDS copy or HBM); `lists_off` / `ids_off` are relative to it.
-// (id_mask: WorldView::id_mask, the list ids less their filling flag)
-template <bool MINDIST>
-__device__ __forceinline__ bool states_exact_rec(const unsigned char* sbase, uint32_t lists_off, uint32_t ids_off,
-                                                 uint32_t id_mask, double rg, double ro, double px, double py,
-                                                 double pz, uint32_t cls, int can_pass, double md) {
-    const double* recs = reinterpret_cast<const double*>(sbase);
-    const uint32_t h = reinterpret_cast<const uint32_t*>(sbase + lists_off)[cls];
-    const uint16_t* ids = reinterpret_cast<const uint16_t*>(sbase + ids_off) + (h >> 12);
-    const uint32_t cnt = h & 4095u;
-    bool hit = false;
-    for (uint32_t j = 0; j < cnt; ++j)
-        hit |= rec_hit<MINDIST>(recs + (size_t)(ids[j] & id_mask) * kRecDoubles, rg, ro, px, py, pz, can_pass != 0, md);
-    return hit;
-}
-
-// rec_hit<false> on a point record (epp_internal.h: kPtDoubles; `pts` the first record, `ide`
-// a list id with its filling flag, worlds with WorldView::id_mask = 0x7FFF only): the record
-// is seven aligned 16-byte reads, the thresholds tx ty tz come inflated from the host (the
-// same IEEE additions and selects, so the same doubles), and "filling" from the id's bit 15:
-// no meta word, no radius select, no additions.  The same conjunction of fp64 comparisons in
-// the same arithmetic (no contraction: -ffp-contract=off), so the booleans are rec_hit's.
-__device__ __forceinline__ bool point_rec_hit(const unsigned char* pts, uint32_t ide, double px, double py, double pz,
-                                              bool can_pass) {
-    typedef double f64x2 __attribute__((ext_vector_type(2)));
-    const uint32_t i = ide & (kIdFill - 1u);
-    f64x2 q[7];
-#pragma unroll
-    for (uint32_t k = 0; k < 7; ++k) q[k] = *reinterpret_cast<const f64x2*>(pts + pt_chunk_off(i, k));
-    const double lox = q[0].x, loy = q[0].y, loz = q[1].x, hix = q[1].y, hiy = q[2].x, hiz = q[2].y;
-    const double cx = q[3].x, cy = q[3].y, cz = q[4].x, c = q[4].y, s = q[5].x;
-    const double tx = q[5].y, ty = q[6].x, tz = q[6].y;
-    // rtree contains(point): strict  src/World.cpp:83
-    const bool in = (lox < px) & (px < hix) & (loy < py) & (py < hiy) & (loz < pz) & (pz < hiz);
-    const bool skip = ((ide & kIdFill) != 0u) & can_pass;  // :92-95
-    // OBB::checkCollisionWithPoint — src/OBB.cpp:63-91 (same evaluation as obb_point_hit)
-    const double dx = px - cx, dy = py - cy, dz = pz - cz;
-    const double lx = c * dx + s * dy;
-    const double ly = c * dy - s * dx;
-    return in & !skip & (fabs(lx) <= tx) & (fabs(ly) <= ty) & (fabs(dz) <= tz);
-}
-
-// states_exact_rec<false> on the point records: `sbase` points at them (LDS copy or HBM).
-__device__ __forceinline__ bool states_exact_pt(const unsigned char* sbase, uint32_t lists_off, uint32_t ids_off,
-                                                double px, double py, double pz, uint32_t cls, int can_pass) {
-    const uint32_t h = reinterpret_cast<const uint32_t*>(sbase + lists_off)[cls];
-    const uint16_t* ids = reinterpret_cast<const uint16_t*>(sbase + ids_off) + (h >> 12);
-    const uint32_t cnt = h & 4095u;
-    bool hit = false;
-    for (uint32_t j = 0; j < cnt; ++j) hit |= point_rec_hit(sbase, ids[j], px, py, pz, can_pass != 0);
     return hit;
 }
 

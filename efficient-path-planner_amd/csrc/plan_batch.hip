@@ -9,8 +9,8 @@
 //   k_pb_number      : the referenced nodes numbered in node order
 //   k_pb_emit        : the results into pinned host memory + the completion slots
 //
-// The state and motion checks between them are the collision kernels (states.hip,
-// motions.hip).  EPP_PB_TRACE=1 times the stages; a -DEPP_PB_ROWS_TL build records
+// The state and motion checks between them are the collision kernels (states_kernels.h,
+// motions_kernels.h).  EPP_PB_TRACE=1 times the stages; a -DEPP_PB_ROWS_TL build records
 // k_pb_rows' per-query timeline (scripts/pb_rows_timeline.py).
 #include <hip/hip_runtime.h>
 

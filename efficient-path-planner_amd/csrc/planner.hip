@@ -9,8 +9,8 @@
 //   k_rev_count / scan / fill / sort : the reverse edges of a k-NN table as a CSR
 //
 // The k-NN itself is knn*.hip (knn_kernels.h), the batched planner plan_batch.hip; both use the scan tag
-// handed out here (planner_common.h).  States and edges are checked by states.hip and
-// motions.hip; the host runs the shortest-path search over the valid edges.
+// handed out here (planner_common.h).  States and edges are checked by the states_*.hip and
+// motions_*.hip kernels; the host runs the shortest-path search over the valid edges.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

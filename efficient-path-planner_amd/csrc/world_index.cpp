@@ -958,7 +958,7 @@ extern "C" epp_status epp_dbg_point_records(const epp_obb* obbs, int32_t n, doub
 
 // Debug entry (not part of include/epp.h): host check of k_states_v5's sparse byte-class
 // encoding -- for every class-grid cell (the zero sentinel included) the lookup the kernel
-// does (occupancy word, rank, class byte; states.hip cls_of) must give the cell's class of
+// does (occupancy word, rank, class byte; states_v5.hip classes_of) must give the cell's class of
 // the u16 table.  Returns the number of mismatching cells (0), or -1 when the world has no
 // byte classes.
 extern "C" int64_t epp_dbg_check_sparse_classes(const epp_obb* obbs, int32_t n, double r_gate, double r_obst) {

@@ -6,8 +6,8 @@ does).  Per kernel: its disassembly (llvm-objdump; no addresses, no raw bytes, b
 targets as offsets from the kernel's start) and its metadata note (VGPRs, SGPRs, LDS bytes,
 private segment, kernarg size).  Prints three lists: kernels only in A, kernels only in B,
 and kernels whose text or metadata differ, with a unified diff for each.  A kernel whose
-parameter list changed (and with it its mangled name) is listed first and then compared with
-its other self.  Exit status 0 when all lists are empty, 1 otherwise.  It only compares.
+parameter list changed or whose template lost or gained a parameter (and with it its mangled
+name changed) is listed first and then compared with its other self.  Exit status 0 when all lists are empty, 1 otherwise.  It only compares.
 """
 import difflib
 import os
@@ -98,9 +98,49 @@ def kernels(lib_path):
 
 
 def _base(name):
-    """The demangled name without its parameter list: epp::k_knn_tile<16>."""
+    """The demangled name without its parameter list, as (template name, template arguments):
+    ("epp::k_knn_tile", ("16",))."""
     out = subprocess.run(["c++filt", name], check=True, capture_output=True, text=True).stdout  # (binutils)
-    return out.replace("(anonymous namespace)::", "").split("(")[0].split()[-1]
+    head = out.replace("(anonymous namespace)::", "").split("(")[0].strip()
+    if not head.endswith(">"):
+        return head.split()[-1], ()
+    depth, lt = 0, len(head)
+    while True:  # the "<" that opens the function's own template arguments
+        lt -= 1
+        depth += (head[lt] == ">") - (head[lt] == "<")
+        if depth == 0:
+            break
+    args, cur = [], ""
+    for ch in head[lt + 1:-1]:
+        depth += (ch == "<") - (ch == ">")
+        if ch == "," and depth == 0:
+            args.append(cur.strip())
+            cur = ""
+        else:
+            cur += ch
+    return head[:lt].split()[-1], tuple(args + [cur.strip()])
+
+
+def _within(short, long):
+    """short can be had from long by deleting template arguments (a dropped template parameter)."""
+    it = iter(long)
+    return all(x in it for x in short)
+
+
+def _resigned(a, b):
+    """{A's name: B's name} for kernels in one build only that are one kernel under two mangled
+    names: the same template and the same template arguments (the function's parameters
+    changed), or one's arguments are the other's with some deleted (a template parameter was
+    dropped or added).  Only pairs that are unique in both directions."""
+    only_a, only_b = sorted(set(a) - set(b)), sorted(set(b) - set(a))
+    base = {k: _base(k) for k in only_a + only_b}
+
+    def same(ka, kb):
+        (na, xa), (nb, xb) = base[ka], base[kb]
+        return na == nb and (_within(xa, xb) or _within(xb, xa))
+    fwd = {ka: [kb for kb in only_b if same(ka, kb)] for ka in only_a}
+    back = {kb: [ka for ka in only_a if same(ka, kb)] for kb in only_b}
+    return {ka: kbs[0] for ka, kbs in fwd.items() if len(kbs) == 1 and len(back[kbs[0]]) == 1}
 
 
 def main():
@@ -108,10 +148,9 @@ def main():
         sys.exit(__doc__)
     a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
     print(f"A = {sys.argv[1]}: {len(a)} kernels\nB = {sys.argv[2]}: {len(b)} kernels")
-    # a kernel template's mangled name holds its parameter types: one whose signature changed is
-    # paired by its name without them and compared under A's name
-    by_base = {_base(k): k for k in set(b) - set(a)}
-    resigned = {k: by_base[_base(k)] for k in sorted(set(a) - set(b)) if _base(k) in by_base}
+    # a kernel template's mangled name holds its template arguments and parameter types: one
+    # whose signature changed is paired by its name without them and compared under A's name
+    resigned = _resigned(a, b)
     print(f"\n== signature changed (compared below as one kernel): {len(resigned)}")
     for ka, kb in resigned.items():
         print(f"  {ka}\n    -> {kb}")

@@ -4,7 +4,7 @@ runs 200 launches, and prints percentiles of each wave's stamps relative to the 
 first stamp: entry, staging barrier, state data arrived, classified, exact path done, end;
 and each wave's own differences (entry -> barrier = the prologue as the wave lived it,
 without the dispatch ramp; barrier -> data arrived; data arrived -> classified; classified
--> exact done).  Eight words per wave (states.hip, kTlWords).
+-> exact done).  Eight words per wave (states_diag.h, kTlWords).
 python scripts/states_timeline.py [noexact] [lib.so]: with a library path, that diagnostics
 build is used as it is (e.g. the parent commit's, built elsewhere)."""
 import ctypes as C
