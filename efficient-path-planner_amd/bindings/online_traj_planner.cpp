@@ -288,6 +288,46 @@ PYBIND11_MODULE(online_traj_planner, m) {
             py::arg("waypoint_sets"), py::arg("v_max"), py::arg("a_max"), py::arg("sampling_interval"),
             py::arg("can_pass_gate") = false)
         .def(
+            "gate_frames",  // the G x 5 gate frame table [cx, cy, cz, cos, sin] of G x 7 gate rows (this build)
+            [](const epp::PathPlanner& self, const py::object& gates) { return from_matrix(self.gateFrames(to_matrix(gates))); },
+            py::arg("gates"))
+        .def(
+            "candidate_gate_passes",  // fit + ordered gate passage of K waypoint sets (this build)
+            [](const epp::PathPlanner& self, const std::vector<py::object>& waypointSets, double vMax, double aMax,
+               double samplingInterval, const py::object& frames, double halfEdge) {
+                std::vector<std::vector<Vec3>> sets;
+                for (const auto& o : waypointSets) {
+                    Matrix w = to_matrix(o);
+                    if (w.cols != 3) throw std::invalid_argument("waypoints must be an (n, 3) array");
+                    std::vector<Vec3> wp;
+                    for (size_t i = 0; i < w.rows; ++i) wp.emplace_back(w(i, 0), w(i, 1), w(i, 2));
+                    sets.push_back(std::move(wp));
+                }
+                const Matrix fr = to_matrix(frames);
+                std::vector<long> chords;
+                std::vector<double> times, offsets;
+                std::vector<int> passed;
+                {
+                    py::gil_scoped_release release;
+                    self.candidateGatePasses(sets, vMax, aMax, samplingInterval, fr, halfEdge, chords, times, passed,
+                                             &offsets);
+                }
+                const py::ssize_t K = (py::ssize_t)sets.size(), G = (py::ssize_t)fr.rows;
+                py::array_t<int64_t> c({K, G});
+                py::array_t<double> t({K, G}), o({K, G, (py::ssize_t)2});
+                py::array_t<int32_t> p(K);
+                for (size_t i = 0; i < chords.size(); ++i) {
+                    c.mutable_data()[i] = chords[i];
+                    t.mutable_data()[i] = times[i];
+                    o.mutable_data()[2 * i] = offsets[2 * i];
+                    o.mutable_data()[2 * i + 1] = offsets[2 * i + 1];
+                }
+                for (size_t i = 0; i < passed.size(); ++i) p.mutable_data()[i] = passed[i];
+                return py::make_tuple(c, t, o, p);
+            },
+            py::arg("waypoint_sets"), py::arg("v_max"), py::arg("a_max"), py::arg("sampling_interval"),
+            py::arg("frames"), py::arg("half_edge") = 0.425)
+        .def(
             "first_hits",  // where every edge s1[i] -> s2[i] is first blocked, and by which OBB (this build)
             [](const epp::PathPlanner& self, const py::object& s1, const py::object& s2, bool canPassGate) {
                 Matrix a = to_matrix(s1), b = to_matrix(s2);
@@ -608,6 +648,22 @@ PYBIND11_MODULE(online_traj_planner, m) {
         .def("get_traj_end_time", &epp::OnlineTrajGenerator::getTrajEndTime)
         .def("get_planned_traj", [](const epp::OnlineTrajGenerator& self) { return from_matrix(self.getPlannedTraj()); })
         // additions of this build
+        .def("get_gate_passes",  // (rows, times): where the planned trajectory passes the gates, in order
+             [](const epp::OnlineTrajGenerator& self) {
+                 std::vector<long> rows;
+                 std::vector<double> times;
+                 {
+                     py::gil_scoped_release release;
+                     self.plannedGatePasses(rows, times);
+                 }
+                 py::array_t<int64_t> r((py::ssize_t)rows.size());
+                 py::array_t<double> t((py::ssize_t)times.size());
+                 for (size_t i = 0; i < rows.size(); ++i) {
+                     r.mutable_data()[i] = rows[i];
+                     t.mutable_data()[i] = times[i];
+                 }
+                 return py::make_tuple(r, t);
+             })
         .def("wait_for_update", &epp::OnlineTrajGenerator::waitForUpdate, py::call_guard<py::gil_scoped_release>())
         .def("recompute_counts",
              [](const epp::OnlineTrajGenerator& self) {

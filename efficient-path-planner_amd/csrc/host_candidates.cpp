@@ -96,7 +96,10 @@ namespace {
 // into firstInvalidRow and its time into rowTimes -- the same upload, fit, stream and single
 // synchronisation.  hit != nullptr: likewise the first hit of every fitted track
 // (epp_traj_first_hit_batch): the entry parameter into *hit, the chord into firstInvalidRow
-// and the hit's time into rowTimes.
+// and the hit's time into rowTimes.  gp != nullptr: instead of the checks, the ordered gate
+// passage of every fitted track (epp_traj_gate_pass_batch) against gp's frame table, uploaded
+// with the waypoints; its n x G outputs take a part of the device block of their own.  Gates
+// are no OBBs: no world takes part.
 struct CandidateClear {
     std::vector<double>& clearance;
     std::vector<int>* nearest;
@@ -105,11 +108,22 @@ struct CandidateHit {
     std::vector<double>& t;
     std::vector<int>* obb;
 };
+struct CandidateGates {
+    const Matrix& frames;  // G x 5
+    double halfEdge;
+    std::vector<long>& chord;   // n x G
+    std::vector<double>& time;  // n x G
+    std::vector<int>& nPassed;  // n
+    std::vector<double>* offsets;  // n x G x 2
+};
 void fit_and_check_candidates(const char* what, const epp_world* world, const std::vector<std::vector<Vec3>>& sets,
                               double v_max, double a_max, double dt, double minDistance, int32_t canPassGate,
                               std::vector<long>& firstInvalidRow, std::vector<double>* rowTimes,
                               std::vector<long>* chords, std::vector<double>* chordTimes,
-                              const CandidateClear* clr = nullptr, const CandidateHit* hit = nullptr) {
+                              const CandidateClear* clr = nullptr, const CandidateHit* hit = nullptr,
+                              const CandidateGates* gp = nullptr) {
+    if (gp && (gp->frames.cols != 5 || gp->frames.rows > 64))
+        throw std::invalid_argument(std::string(what) + ": the gate frame table must be (G <= 64) x 5");
     for (const auto& s : sets)
         if (s.size() < 2) throw std::invalid_argument("At least two waypoints are required");
     const size_t n = sets.size();
@@ -124,6 +138,13 @@ void fit_and_check_candidates(const char* what, const epp_world* world, const st
     if (hit) {
         hit->t.assign(n, HUGE_VAL);
         if (hit->obb) hit->obb->assign(n, -1);
+    }
+    const size_t G = gp ? gp->frames.rows : 0;
+    if (gp) {
+        gp->chord.assign(n * G, -1);
+        gp->time.assign(n * G, -1.0);
+        gp->nPassed.assign(n, 0);
+        if (gp->offsets) gp->offsets->assign(n * G * 2, NAN);
     }
     if (n == 0) return;
     // host image of the upload: [waypoints | offsets]; device block: [wp | T | coeffs |
@@ -158,18 +179,27 @@ void fit_and_check_candidates(const char* what, const epp_world* world, const st
     auto after = [](size_t o, size_t b) { return (o + b + 255) & ~(size_t)255; };  // 256-B aligned parts
     const size_t o_wp = 0, o_T = after(o_wp, total * 24), o_C = after(o_T, nseg * 8), o_ft = after(o_C, nseg * 240),
                  o_fi = after(o_ft, n * 8), o_ct = after(o_fi, n * 8), o_ci = after(o_ct, n * 8),
-                 o_off = after(o_ci, n * 8), o_st = after(o_off, (n + 1) * 4), bytes = after(o_st, n * 4);
+                 o_off = after(o_ci, n * 8), o_st = after(o_off, (n + 1) * 4), o_gf = after(o_st, n * 4),
+                 o_gc = after(o_gf, G * 40), o_gt = after(o_gc, n * G * 8), o_go = after(o_gt, n * G * 8),
+                 o_gn = after(o_go, n * G * 16), bytes = after(o_gn, gp ? n * 4 : 0);
     need(epp_malloc(&d.buf, bytes));
     need(epp_stream_create(&d.st));
     char* base = static_cast<char*>(d.buf);
     need(epp_memcpy_h2d_async(base + o_wp, wp.data(), total * 24, d.st));
     need(epp_memcpy_h2d_async(base + o_off, off.data(), (n + 1) * 4, d.st));
+    if (G) need(epp_memcpy_h2d_async(base + o_gf, gp->frames.data.data(), G * 40, d.st));
     double* d_T = reinterpret_cast<double*>(base + o_T);
     double* d_C = reinterpret_cast<double*>(base + o_C);
     const int32_t* d_off = reinterpret_cast<const int32_t*>(base + o_off);
     need(epp_minsnap_batch(reinterpret_cast<const double*>(base + o_wp), d_off, (int32_t)n, v_max, a_max, nullptr,
                            nullptr, d_T, d_C, reinterpret_cast<int32_t*>(base + o_st), d.st));
-    if (clr)  // (the chord slots hold the clearance and the nearest OBB)
+    if (gp)
+        need(epp_traj_gate_pass_batch(reinterpret_cast<const double*>(base + o_gf), (int32_t)G, gp->halfEdge, d_T, d_C,
+                                      d_off, (int32_t)n, dt, reinterpret_cast<int64_t*>(base + o_gc),
+                                      reinterpret_cast<double*>(base + o_gt),
+                                      gp->offsets ? reinterpret_cast<double*>(base + o_go) : nullptr,
+                                      reinterpret_cast<int32_t*>(base + o_gn), d.st));
+    else if (clr)  // (the chord slots hold the clearance and the nearest OBB)
         need(epp_traj_clearance_batch(world, d_T, d_C, d_off, (int32_t)n, dt, reinterpret_cast<double*>(base + o_ct),
                                       reinterpret_cast<int64_t*>(base + o_fi), reinterpret_cast<double*>(base + o_ft),
                                       reinterpret_cast<int32_t*>(base + o_ci), d.st));
@@ -190,8 +220,20 @@ void fit_and_check_candidates(const char* what, const epp_world* world, const st
     std::vector<int64_t> rows(n), crows(n);
     std::vector<double> times(n), ctimes(n);
     need(epp_memcpy_d2h_async(status.data(), base + o_st, n * 4, d.st));
-    need(epp_memcpy_d2h_async(rows.data(), base + o_fi, n * 8, d.st));
-    need(epp_memcpy_d2h_async(times.data(), base + o_ft, n * 8, d.st));
+    if (!gp) {
+        need(epp_memcpy_d2h_async(rows.data(), base + o_fi, n * 8, d.st));
+        need(epp_memcpy_d2h_async(times.data(), base + o_ft, n * 8, d.st));
+    }
+    std::vector<int64_t> gchord(n * G);
+    std::vector<int32_t> gpassed(gp ? n : 0);
+    if (gp) {
+        need(epp_memcpy_d2h_async(gpassed.data(), base + o_gn, n * 4, d.st));
+        if (G) {
+            need(epp_memcpy_d2h_async(gchord.data(), base + o_gc, n * G * 8, d.st));
+            need(epp_memcpy_d2h_async(gp->time.data(), base + o_gt, n * G * 8, d.st));
+            if (gp->offsets) need(epp_memcpy_d2h_async(gp->offsets->data(), base + o_go, n * G * 16, d.st));
+        }
+    }
     if (chords) {
         need(epp_memcpy_d2h_async(crows.data(), base + o_ci, n * 8, d.st));
         need(epp_memcpy_d2h_async(ctimes.data(), base + o_ct, n * 8, d.st));
@@ -214,6 +256,10 @@ void fit_and_check_candidates(const char* what, const epp_world* world, const st
     if (chords && chordTimes) *chordTimes = ctimes;
     if (clr && clr->nearest) clr->nearest->assign(near.begin(), near.end());
     if (hit && hit->obb) hit->obb->assign(near.begin(), near.end());
+    if (gp) {
+        gp->chord.assign(gchord.begin(), gchord.end());
+        gp->nPassed.assign(gpassed.begin(), gpassed.end());
+    }
 }
 }  // namespace
 
@@ -223,6 +269,34 @@ void PathPlanner::candidateFirstHits(const std::vector<std::vector<Vec3>>& sets,
     const CandidateHit hit{t, obb};
     fit_and_check_candidates("candidateFirstHits", sets.empty() ? nullptr : worldPtr->device(), sets, v_max, a_max, dt,
                              0.0, canPassGate ? 1 : 0, chord, time, nullptr, nullptr, nullptr, &hit);
+}
+
+// The gate centre and cos / sin of the yaw per gate row: getGateCenterAndNormal's centre
+// (src/OnlineTrajGenerator.cpp:50-70) and checkGatePassed's c, s (:236).
+Matrix PathPlanner::gateFrames(const Matrix& gates) const {
+    if (gates.rows && gates.cols < 7) throw std::invalid_argument("gateFrames: gate rows have 7 columns");
+    Matrix f(gates.rows, 5);
+    for (size_t g = 0; g < gates.rows; ++g) {
+        const double* r = gates.row(g);
+        if (r[3] != 0 || r[4] != 0)
+            throw std::invalid_argument("gateFrames: Only simple rotation around z axis is supported");
+        f(g, 0) = r[0];
+        f(g, 1) = r[1];
+        f(g, 2) = r[2] + configParser->getObjectPropertiesByTypeId((int)r[6]).height;
+        f(g, 3) = std::cos(r[5]);
+        f(g, 4) = std::sin(r[5]);
+    }
+    return f;
+}
+
+void PathPlanner::candidateGatePasses(const std::vector<std::vector<Vec3>>& sets, double v_max, double a_max, double dt,
+                                      const Matrix& frames, double halfEdge, std::vector<long>& chord,
+                                      std::vector<double>& time, std::vector<int>& nPassed,
+                                      std::vector<double>* offsets) const {
+    std::vector<long> rows;
+    const CandidateGates gp{frames, halfEdge, chord, time, nPassed, offsets};
+    fit_and_check_candidates("candidateGatePasses", nullptr, sets, v_max, a_max, dt, 0.0, 0, rows, nullptr, nullptr,
+                             nullptr, nullptr, nullptr, &gp);
 }
 
 void PathPlanner::candidateClearances(const std::vector<std::vector<Vec3>>& sets, double v_max, double a_max, double dt,

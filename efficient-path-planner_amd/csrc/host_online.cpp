@@ -16,6 +16,8 @@
 #include "epp/OptimalTimeParametrizer.h"
 #include "epp/TrajInterpolation.h"
 #include "epp/trajectory_generator.h"
+#include "epp.h"
+#include "gate_pass.h"
 
 namespace epp {
 
@@ -190,6 +192,57 @@ bool OnlineTrajGenerator::checkGatePassed(const Vec3& pos1, const Vec3& pos2, in
         if (std::abs(m.x) <= edgeLength && std::abs(m.z) <= edgeLength) return true;
     }
     return false;
+}
+
+// Where the planned trajectory passes the gates, in order: checkGatePassed's predicate
+// (gate_pass.h) for every step row j -> row j + 1 and every gate in one launch
+// (epp_gates_crossed), then the ordered resolution on the masks.
+void OnlineTrajGenerator::plannedGatePasses(std::vector<long>& rows, std::vector<double>& times) const {
+    const Matrix frames = pathPlanner.gateFrames(nominalGatePositionAndType);
+    const size_t G = frames.rows;
+    if (G > (size_t)kMaxGates) throw std::invalid_argument("plannedGatePasses: more than 64 gates");
+    const Matrix traj = getPlannedTraj();
+    rows.assign(G, -1);
+    times.assign(G, -1.0);
+    if (traj.rows < 2 || G == 0) return;
+    const size_t R = traj.rows, n = R - 1;
+    const double halfEdge = 0.425;  // src/OnlineTrajGenerator.cpp:249
+    std::vector<double> xyz(R * 3);
+    for (size_t i = 0; i < R; ++i) {
+        xyz[3 * i] = traj(i, 0);
+        xyz[3 * i + 1] = traj(i, 3);
+        xyz[3 * i + 2] = traj(i, 6);
+    }
+    struct Dev {  // released on every way out
+        void* buf = nullptr;
+        ~Dev() {
+            if (buf) (void)epp_free(buf);
+        }
+    } d;
+    auto need = [](epp_status rc) {
+        if (rc == EPP_ERR_INVALID_ARGUMENT) throw std::invalid_argument(epp_last_error());
+        if (rc != EPP_OK) throw std::runtime_error(std::string("plannedGatePasses: ") + epp_last_error());
+    };
+    // device block: [frames | row positions | masks]
+    const size_t o_xyz = G * kGateDoubles * 8, o_mask = o_xyz + R * 24;
+    need(epp_malloc(&d.buf, o_mask + n * 8));
+    char* base = static_cast<char*>(d.buf);
+    need(epp_memcpy_h2d(base, frames.data.data(), o_xyz, nullptr));
+    need(epp_memcpy_h2d(base + o_xyz, xyz.data(), R * 24, nullptr));
+    const double* d_xyz = reinterpret_cast<const double*>(base + o_xyz);
+    need(epp_gates_crossed(reinterpret_cast<const double*>(base), (int32_t)G, halfEdge, d_xyz, d_xyz + 3, (int64_t)n,
+                           reinterpret_cast<uint64_t*>(base + o_mask), nullptr));
+    std::vector<uint64_t> mask(n);
+    need(epp_memcpy_d2h(mask.data(), base + o_mask, n * 8, nullptr));
+    size_t j = 0;
+    for (size_t g = 0; g < G; ++g) {  // (the same step may pass consecutive gates)
+        while (j < n && !((mask[j] >> g) & 1u)) ++j;
+        if (j == n) break;
+        const GateCross c = gate_cross(frames.row(g), halfEdge, xyz[3 * j], xyz[3 * j + 1], xyz[3 * j + 2],
+                                       xyz[3 * j + 3], xyz[3 * j + 4], xyz[3 * j + 5]);
+        rows[g] = (long)j;
+        times[g] = traj(j, 9) + c.u() * (traj(j + 1, 9) - traj(j, 9));
+    }
 }
 
 // OnlineTrajGenerator::updateGatePos — src/OnlineTrajGenerator.cpp:123-226

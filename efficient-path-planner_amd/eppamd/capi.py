@@ -101,6 +101,8 @@ def lib() -> C.CDLL:
             "epp_traj_clearance_batch": (i32, [vp, vp, vp, vp, i32, dp, vp, vp, vp, vp, vp]),
             "epp_motions_first_hit": (i32, [vp, vp, vp, i64, i32, vp, vp, vp]),
             "epp_traj_first_hit_batch": (i32, [vp, vp, vp, vp, i32, dp, i32, vp, vp, vp, vp, vp]),
+            "epp_gates_crossed": (i32, [vp, i32, dp, vp, vp, i64, vp, vp]),
+            "epp_traj_gate_pass_batch": (i32, [vp, i32, dp, vp, vp, vp, i32, dp, vp, vp, vp, vp, vp]),
             "epp_generate_trajectory_limited_host": (i32, [vp, i32, dp, dp, dp, dp, vp, vp,
                                                            C.POINTER(C.POINTER(C.c_double)), C.POINTER(i64),
                                                            C.POINTER(C.c_double)]),
@@ -165,7 +167,7 @@ EXPORTED = [
     "epp_comm_set_timeout", "epp_comm_abort", "epp_check_and_generate_trajectory_host",
     "epp_traj_peaks", "epp_traj_scale_to_limits", "epp_generate_trajectory_limited_host",
     "epp_traj_check_batch", "epp_traj_sweep_batch", "epp_states_clearance", "epp_traj_clearance_batch",
-    "epp_motions_first_hit", "epp_traj_first_hit_batch",
+    "epp_motions_first_hit", "epp_traj_first_hit_batch", "epp_gates_crossed", "epp_traj_gate_pass_batch",
 ]
 
 
@@ -521,6 +523,54 @@ def _upload_tracks(Ts, Cs):
         d_T.upload(T)
         d_C.upload(Cf)
     return d_T, d_C, DeviceBuffer.from_array(off), off, nseg
+
+
+GATE_HALF_EDGE = 0.425  # OnlineTrajGenerator::checkGatePassed's edgeLength (src/OnlineTrajGenerator.cpp:249)
+
+
+def gate_frames(centres, yaws) -> np.ndarray:
+    """The gate frame table of gates_crossed / trajectory_gate_passes: (G, 5) rows
+    [cx, cy, cz, cos(yaw), sin(yaw)] from the gate centres (G, 3) and yaws (G), with numpy's
+    cos / sin.  (PathPlanner.gate_frames builds it from gate rows and the config's heights.)"""
+    centres = np.asarray(centres, np.float64).reshape(-1, 3)
+    yaws = np.asarray(yaws, np.float64).reshape(-1)
+    assert len(yaws) == len(centres)
+    return np.ascontiguousarray(np.column_stack([centres, np.cos(yaws), np.sin(yaws)]))
+
+
+def gates_crossed(frames, half_edge: float, s1: np.ndarray, s2: np.ndarray) -> np.ndarray:
+    """epp_gates_crossed: per edge s1[i] -> s2[i] a uint64 whose bit g says that the edge
+    crosses gate g of the frame table (at most 64 gates) from its negative to its positive
+    side within half_edge of its centre (checkGatePassed).  Returns uint64[n]."""
+    frames = np.ascontiguousarray(frames, np.float64).reshape(-1, 5)
+    s1 = np.ascontiguousarray(s1, np.float64).reshape(-1, 3)
+    s2 = np.ascontiguousarray(s2, np.float64).reshape(-1, 3)
+    n = len(s1)
+    assert len(s2) == n
+    d_f, d1, d2 = DeviceBuffer.from_array(frames), DeviceBuffer.from_array(s1), DeviceBuffer.from_array(s2)
+    d_m = DeviceBuffer(8 * n)
+    check(lib().epp_gates_crossed(d_f.ptr, len(frames), float(half_edge), d1.ptr, d2.ptr, n, d_m.ptr, None))
+    sync()
+    return d_m.download(np.uint64, n)
+
+
+def trajectory_gate_passes(frames, half_edge: float, Ts, Cs, dt: float):
+    """epp_traj_gate_pass_batch on the lists minsnap_batch returns: per track and gate the
+    chord row j -> row j + 1 that passes the gate after the gates before it (-1: unpassed),
+    its split time (-1.0) and the crossing's midpoint offsets in the gate frame (NaN), and per
+    track the number of leading gates passed.  Returns (int64[n, G], float64[n, G],
+    float64[n, G, 2], int32[n])."""
+    frames = np.ascontiguousarray(frames, np.float64).reshape(-1, 5)
+    nt, G = len(Ts), len(frames)
+    d_T, d_C, d_off, _, _ = _upload_tracks(Ts, Cs)
+    d_f = DeviceBuffer.from_array(frames)
+    d_chord, d_time, d_o, d_np = (DeviceBuffer(8 * nt * G), DeviceBuffer(8 * nt * G), DeviceBuffer(16 * nt * G),
+                                  DeviceBuffer(4 * nt))
+    check(lib().epp_traj_gate_pass_batch(d_f.ptr, G, float(half_edge), d_T.ptr, d_C.ptr, d_off.ptr, nt, float(dt),
+                                         d_chord.ptr, d_time.ptr, d_o.ptr, d_np.ptr, None))
+    sync()
+    return (d_chord.download(np.int64, nt * G).reshape(nt, G), d_time.download(np.float64, nt * G).reshape(nt, G),
+            d_o.download(np.float64, nt * G * 2).reshape(nt, G, 2), d_np.download(np.int32, nt))
 
 
 def traj_peaks(Ts, Cs):

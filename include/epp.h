@@ -42,6 +42,9 @@
  *       what MotionValidator::checkMotion(s1, s2, lastValid) (src/MotionValidator.cpp:19-22, a
  *       stub there) needs: where along a straight edge World::checkRayValid first fails and
  *       against which OBB, per edge and for the first failing chord of every fitted track.
+ *   epp_gates_crossed / epp_traj_gate_pass_batch
+ *       OnlineTrajGenerator::checkGatePassed (src/OnlineTrajGenerator.cpp:228-256), per edge
+ *       and gate, and as the ordered passage of every fitted track's chords with split times.
  */
 #ifndef EPP_H_
 #define EPP_H_
@@ -359,6 +362,52 @@ epp_status epp_motions_first_hit(const epp_world* w, const double* s1, const dou
 epp_status epp_traj_first_hit_batch(const epp_world* w, const double* seg_times, const double* coeffs,
                                     const int32_t* wp_offsets, int32_t n_tracks, double dt, int32_t can_pass_gate,
                                     int64_t* chord, double* t_hit, double* time, int32_t* obb, void* stream);
+
+/* ---- gate passage: which gates an edge crosses, and which gates, in order, a fitted track
+ * passes and when (device pointers).  No epp_world takes part: gates are given as a frame
+ * table, n_gates x 5 f64 on the device, row g = [cx, cy, cz, c, s] with (cx, cy, cz) the gate
+ * centre (the gate position plus (0, 0, height[type]), getGateCenterAndNormal,
+ * src/OnlineTrajGenerator.cpp:50-70) and c, s = cos(yaw), sin(yaw), computed once on the host;
+ * the kernels call no trigonometric function.  half_edge: half the opening's edge (the
+ * reference's constant is 0.425).  The edge p1 -> p2 crosses gate g iff
+ * (OnlineTrajGenerator::checkGatePassed, src/OnlineTrajGenerator.cpp:228-256), every operation
+ * one IEEE fp64 multiply, add, subtract or divide in this association, nothing fused:
+ *   t1 = p1 - centre;  g1 = (c*t1.x - s*t1.y,  s*t1.x + c*t1.y,  t1.z)    (same for p2 -> g2)
+ *   g1.y < 0  &&  g2.y > 0  &&  |(g1.x + g2.x) / 2| <= half_edge  &&  |(g1.z + g2.z) / 2| <= half_edge
+ * From negative to positive gate-frame y only; both inequalities are strict (a point exactly on
+ * the gate plane crosses on neither side); NaN compares false.  With a crossing go the plane
+ * parameter u = g1.y / (g1.y - g2.y) and the two midpoint offsets the predicate tested.
+ *
+ * epp_gates_crossed: bit g of mask[i] (n, device uint64) is the predicate of edge s1[i] ->
+ * s2[i] (n x 3 f64 each) for gate g; n_gates is 0..64, n_gates == 0 writes zeros.
+ * Stream-ordered, no host synchronisation and no allocation, so the call can be captured
+ * (epp_graph_begin).  EPP_ERR_INVALID_ARGUMENT (before any device work) for n_gates < 0 or
+ * > 64, half_edge negative or not finite, n < 0, or a NULL s1, s2 or mask (or gates with
+ * n_gates > 0) with n > 0; n == 0 launches nothing. */
+epp_status epp_gates_crossed(const double* gates, int32_t n_gates, double half_edge, const double* s1,
+                             const double* s2, int64_t n, uint64_t* mask, void* stream);
+/* The ordered gate passage of every track of a batch in the layout of epp_minsnap_batch,
+ * straight from the coefficients, in one launch and without writing a row.  Chord j of track k
+ * is row j -> row j + 1 of Trajectory::evaluateRange(0, max_time, dt) (positions: columns
+ * 0 / 3 / 6 of epp_sample_batch's rows).  With c_-1 = 0, c_g is the smallest j >= c_g-1 whose
+ * chord crosses gate g (the same chord may pass consecutive gates; a gate listed twice is
+ * found twice on a track that goes round twice); without one, gate g and every later gate are
+ * unpassed.  chord[k * n_gates + g] (device int64) = c_g, -1 if unpassed;
+ * time[k * n_gates + g] (device f64, may be NULL) = t_j + u * (t_j+1 - t_j) on the time
+ * columns epp_sample_batch writes with t0 == NULL (one subtract, one multiply, one add,
+ * unfused), -1.0 if unpassed; offset[(k * n_gates + g) * 2 + {0, 1}] (device f64, may be NULL)
+ * the two midpoint offsets, NaN if unpassed; n_passed[k] (device int32, required) the number
+ * of leading gates passed.  A track with fewer than two rows (one waypoint, the NaN times of a
+ * failed fit) passes nothing.  The answers are those of epp_sample_count + epp_sample_batch +
+ * epp_gates_crossed(s1 = rows j, s2 = rows j + 1) and the ordered resolution, bit for bit.
+ * Stream-ordered, no host synchronisation and no allocation, so the call can be captured.
+ * EPP_ERR_INVALID_ARGUMENT (before any device work) as epp_gates_crossed for n_gates and
+ * half_edge, for n_tracks < 0, dt <= 0 or not finite, or a NULL seg_times, coeffs, wp_offsets
+ * or n_passed (or gates or chord with n_gates > 0) with n_tracks > 0; n_tracks == 0 launches
+ * nothing. */
+epp_status epp_traj_gate_pass_batch(const double* gates, int32_t n_gates, double half_edge, const double* seg_times,
+                                    const double* coeffs, const int32_t* wp_offsets, int32_t n_tracks, double dt,
+                                    int64_t* chord, double* time, double* offset, int32_t* n_passed, void* stream);
 
 /* ---- batch planner building blocks (device pointers) ------------------------------- */
 /* Replace OMPL's sampler / nearest-neighbour structure behind PathPlanner::planPath

@@ -43,6 +43,13 @@ public:
     std::vector<double> sampleTraj(double currentTime) const;
     double getTrajEndTime() const;
     Matrix getPlannedTraj() const;
+    // Where the planned trajectory passes the gates, in order (an addition of this build):
+    // epp_gates_crossed (include/epp.h) on its consecutive rows against the current gate
+    // poses (half edge 0.425, checkGatePassed's), then per gate g the first row j at or after
+    // gate g - 1's whose step row j -> row j + 1 crosses it.  rows[g] = j and times[g] = the
+    // split time t_j + u * (t_j+1 - t_j) on the rows' time column; -1 and -1.0 for the first
+    // gate without such a step and every gate after it.  At most 64 gates.
+    void plannedGatePasses(std::vector<long>& rows, std::vector<double>& times) const;
 
     const std::vector<Vec3>& getCheckpoints() const { return checkpoints; }
     // waypoints of the last (re)planned trajectory, after includeGates2

@@ -153,6 +153,28 @@ public:
     void candidateFirstHits(const std::vector<std::vector<Vec3>>& waypointSets, double v_max, double a_max, double dt,
                             bool canPassGate, std::vector<long>& chord, std::vector<double>& t,
                             std::vector<double>* time = nullptr, std::vector<int>* obb = nullptr) const;
+    // The gate frame table of epp_gates_crossed / epp_traj_gate_pass_batch (include/epp.h) for
+    // G gate rows [x, y, z, rx, ry, yaw, type] (an addition of this build): G x 5 rows
+    // [cx, cy, cz, cos(yaw), sin(yaw)], the centre being the position plus (0, 0, height) of the
+    // gate's type in this planner's config (getGateCenterAndNormal,
+    // src/OnlineTrajGenerator.cpp:50-70), cos / sin from std::cos / std::sin.  Throws
+    // std::invalid_argument for a row with a rotation about x or y, which
+    // getGateCenterAndNormal rejects, and for rows of fewer than 7 columns.
+    Matrix gateFrames(const Matrix& gates) const;
+    // Which gates, in order, each of K candidate waypoint sets' trajectories passes, and when
+    // (an addition of this build), to rank candidates after validity: the fit of every set as
+    // above and, on the same stream with one synchronisation, epp_traj_gate_pass_batch
+    // (include/epp.h) of the fits' chords at dt against `frames` (gateFrames' table, G <= 64
+    // rows) with the opening's half edge `halfEdge` (the reference's constant: 0.425).  Row-major
+    // K x G: chord[k * G + g] the chord row j -> row j + 1 of set k that passes gate g after
+    // the gates before it, -1 if unpassed; time its split time, -1.0 if unpassed; offsets
+    // (optional, K x G x 2) the crossing's midpoint offsets in the gate frame (x, z), NaN if
+    // unpassed.  nPassed[k]: the leading gates set k passes.  Throws as
+    // checkCandidateTrajectories.
+    void candidateGatePasses(const std::vector<std::vector<Vec3>>& waypointSets, double v_max, double a_max, double dt,
+                             const Matrix& frames, double halfEdge, std::vector<long>& chord,
+                             std::vector<double>& time, std::vector<int>& nPassed,
+                             std::vector<double>* offsets = nullptr) const;
     std::vector<Vec3> includeGates2(std::vector<std::vector<Vec3>> waypoints) const;
     // planPaths of consecutive gate-to-gate segments, then includeGates2 of their paths (an
     // addition of this build, for OnlineTrajGenerator::preComputeTraj): the same answers as
