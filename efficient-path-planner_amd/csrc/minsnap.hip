@@ -625,8 +625,11 @@ __global__ __launch_bounds__(kWave) void k_sample_rows(const double* __restrict_
 // times (Nfabian with the host's libm, as the reference) and Trajectory::evaluateRange's
 // `acc += dt` recurrence (sample times and segments, exact).  G workgroups each own a
 // slice of the rows; every one of them solves the (small) min-snap problem itself with
-// those times (solve_track — the same arithmetic, so the same coefficients) while its
-// slice's sample data arrives from the host, then evaluates its rows
+// those times (solve_track — the same arithmetic in every one of them, so the same
+// coefficients in all G; NOT the batch kernel's bits: k_minsnap runs solve_track with 64
+// threads and the refinement step, this path with 256 and without it, so the two fits differ
+// in the last bits, each within the fit's accuracy — tests/test_gpu_sample_batch.py) while
+// its slice's sample data arrives from the host, then evaluates its rows
 // (Polynomial::evaluate) and writes them to the host: G CUs writing in parallel (one CU's
 // PCIe writes are slow) and no hand-off of the coefficients between workgroups.
 // Completion is published in host memory (workgroup 0: the status; every workgroup: its

@@ -525,6 +525,69 @@ def _upload_tracks(Ts, Cs):
     return d_T, d_C, DeviceBuffer.from_array(off), off, nseg
 
 
+def sample_count(Ts, dt: float) -> np.ndarray:
+    """epp_sample_count on the segment-time lists minsnap_batch returns: the number of rows
+    Trajectory::evaluateRange(0, max_time, dt) gives per track.  Returns int64[n]."""
+    nt = len(Ts)
+    if nt == 0:
+        return np.zeros(0, np.int64)
+    Ts = [np.asarray(t, np.float64).ravel() for t in Ts]
+    off = np.zeros(nt + 1, np.int32)
+    off[1:] = np.cumsum([len(t) + 1 for t in Ts])
+    d_T, d_off = DeviceBuffer.from_array(np.concatenate(Ts + [np.zeros(1)])), DeviceBuffer.from_array(off)
+    d_cnt = DeviceBuffer(8 * nt)
+    check(lib().epp_sample_count(d_T.ptr, d_off.ptr, nt, float(dt), d_cnt.ptr, None))
+    sync()
+    return d_cnt.download(np.int64, nt)
+
+
+def sample_batch(Ts, Cs, dt: float, t0=None, row_offsets=None, n_rows=None, fill=None) -> np.ndarray:
+    """epp_sample_batch on the lists minsnap_batch returns: the rows [x, vx, ax, y, vy, ay, z,
+    vz, az, t] of every track, track k's time column offset by t0[k] (None: the call's NULL).
+
+    By default the tracks' rows follow each other (the exclusive scan of sample_count) and the
+    buffer holds exactly them.  row_offsets (int64[n], track k's first row) with n_rows (the
+    buffer's size in rows): the caller lays the tracks out; every track's range must lie inside
+    the buffer (checked here against sample_count, before the launch).  fill: the float64 bit
+    pattern (a u64) every slot of the buffer holds before the launch, None: zeros.
+    Returns float64[n_rows, 10]."""
+    nt = len(Ts)
+    dt = float(dt)
+    d_T, d_C, d_off, _, _ = _upload_tracks(Ts, Cs)
+    cnt = np.zeros(nt, np.int64)
+    if nt:
+        d_cnt = DeviceBuffer(8 * nt)
+        check(lib().epp_sample_count(d_T.ptr, d_off.ptr, nt, dt, d_cnt.ptr, None))
+        sync()
+        cnt = d_cnt.download(np.int64, nt)
+    if row_offsets is None:
+        if n_rows is not None:
+            raise ValueError("sample_batch: n_rows goes with row_offsets")
+        roff = np.zeros(nt, np.int64)
+        roff[1:] = np.cumsum(cnt)[:-1]
+        n_rows = int(cnt.sum())
+    else:
+        roff = np.ascontiguousarray(row_offsets, np.int64).reshape(-1)
+        if n_rows is None or len(roff) != nt:
+            raise ValueError("sample_batch: row_offsets needs one entry per track and n_rows")
+        n_rows = int(n_rows)
+        if n_rows < 0 or (roff < 0).any() or (roff + cnt > n_rows).any():
+            raise ValueError("sample_batch: a track's rows do not fit the buffer")
+    d_rows = _filled(80 * max(n_rows, 1), fill)
+    if nt:
+        d_t0 = None
+        if t0 is not None:
+            t0 = np.ascontiguousarray(t0, np.float64).reshape(-1)
+            if len(t0) != nt:
+                raise ValueError("sample_batch: t0 needs one entry per track")
+            d_t0 = DeviceBuffer.from_array(t0)
+        d_roff = DeviceBuffer.from_array(roff)
+        check(lib().epp_sample_batch(d_T.ptr, d_C.ptr, d_off.ptr, nt, dt, d_t0.ptr if d_t0 else None, d_roff.ptr,
+                                     d_rows.ptr, None))
+        sync()
+    return d_rows.download(np.float64, n_rows * 10).reshape(n_rows, 10)
+
+
 GATE_HALF_EDGE = 0.425  # OnlineTrajGenerator::checkGatePassed's edgeLength (src/OnlineTrajGenerator.cpp:249)
 
 

@@ -9,6 +9,8 @@ device's Horner ordering); the magnitude re-evaluated at the reported time withi
 relative of the reported peak (the time itself is ill-conditioned at a flat top and is not
 compared with the truth's).
 """
+import functools
+
 import numpy as np
 import pytest
 
@@ -178,19 +180,21 @@ def _scale_fit():
     return _SCALE_FIT["fit"]
 
 
-@pytest.mark.parametrize("v_max,a_max", [(1.0, 2.0), (3.0, 0.6)])
-def test_scale_to_limits(v_max, a_max):
-    Ts, Cs = _scale_fit()
+def _check_scaling(Ts, Cs, v_max, a_max, truth=None):
+    """epp_traj_scale_to_limits on one batch against the truth's loop (F.scale_to_limits per
+    track; truth: precomputed results by track index).  Returns how many tracks were within
+    range, decided by the velocity branch, and by the acceleration (sqrt) branch."""
     Tn, Cn, sc, st = capi.scale_to_limits(Ts, Cs, v_max, a_max)
     assert (st == 0).all()
     pk, pst = capi.traj_peaks(Tn, Cn)
     assert (pst == 0).all()
     rs = np.random.RandomState(3)
     n_in = n_v = n_a = 0
-    for k in range(64):
+    for k in range(len(Ts)):
         before = F.traj_peaks(Ts[k], Cs[k])
         vv, av = before[0] / v_max, before[2] / a_max
-        _, _, s_truth, within, rounds = F.scale_to_limits(Ts[k], Cs[k], v_max, a_max)
+        _, _, s_truth, within, rounds = (truth[k] if truth and k in truth
+                                         else F.scale_to_limits(Ts[k], Cs[k], v_max, a_max))
         assert within and rounds <= 2
         print(f"track {k}: gpu scale {sc[k]!r} truth {s_truth!r} peaks after {pk[k, 0]!r} {pk[k, 2]!r}")
         assert abs(sc[k] - s_truth) <= 1e-9 * s_truth, (k, sc[k], s_truth)
@@ -199,6 +203,7 @@ def test_scale_to_limits(v_max, a_max):
         if vv <= 1 + 1e-3 and av <= 1 + 1e-3:
             n_in += 1
             assert sc[k] == 1.0 and np.array_equal(Tn[k], Ts[k]) and np.array_equal(Cn[k], Cs[k]), k
+            assert Tn[k].tobytes() == Ts[k].tobytes() and Cn[k].tobytes() == Cs[k].tobytes(), k
         else:
             n_v += vv >= np.sqrt(av)
             n_a += vv < np.sqrt(av)
@@ -207,6 +212,14 @@ def test_scale_to_limits(v_max, a_max):
             d = np.abs(F.position(Tn[k], Cn[k], sc[k] * tau) - F.position(Ts[k], Cs[k], tau)).max()
             assert d < 1e-9, (k, tau, d)
     print("within range", n_in, "velocity branch", n_v, "acceleration branch", n_a)
+    return n_in, n_v, n_a
+
+
+@pytest.mark.parametrize("v_max,a_max", [(1.0, 2.0), (3.0, 0.6)])
+def test_scale_to_limits(v_max, a_max):
+    Ts, Cs = _scale_fit()
+    assert len(Ts) == 64
+    n_in, n_v, n_a = _check_scaling(Ts, Cs, v_max, a_max)
     assert n_in > 0 and (n_v > 0 if (v_max, a_max) == (1.0, 2.0) else n_a > 0)
 
 
@@ -247,3 +260,128 @@ def test_generate_trajectory_limited(seed):
     pk, _ = capi.traj_peaks(Ts, Cs)
     v_peak, a_peak = PT.max_velocity_and_acceleration(wp, 1.0, 2.0)
     assert v_peak == pk[0, 0] and a_peak == pk[0, 2]
+
+
+# ---- 7. long tracks ---------------------------------------------------------------------
+# An "ompl"-simplified track has about 330 waypoints.  The limit kernels' loops make a second
+# trip only on such tracks: the in-place coefficient rewrite (256 threads over M * 3
+# polynomials) from M = 86, the time rewrite and track_invalid's loop over T from M = 257,
+# track_invalid's loop over the coefficients from M = 9.  The tracks: the first M segments of
+# eight 41-segment fits laid end to end (the peaks are per segment, a joint between two fits is
+# one more segment boundary, where _magnitude_at accepts either neighbour).
+LONG_M = (85, 86, 256, 257, 328)
+LIMIT_PAIRS = ((1.0, 2.0), (3.0, 0.6))
+
+
+@functools.lru_cache(maxsize=None)
+def _long_tracks():
+    tracks = [synth.random_track_waypoints(20000 + 31 * 41 + k, 41) for k in range(8)]
+    Ts, Cs = _fit(tracks, 41)
+    T, Cf = np.concatenate(Ts), np.concatenate(Cs)
+    assert len(T) == 328
+    return [T[:M].copy() for M in LONG_M], [Cf[:M].copy() for M in LONG_M]
+
+
+@functools.lru_cache(maxsize=None)
+def _ragged_fit():
+    tracks = [synth.random_track_waypoints(900 + k, 1 + (k * 7) % 30) for k in range(40)]
+    return _fit(tracks, 77)
+
+
+@functools.lru_cache(maxsize=None)
+def _long_scale_truth(v_max, a_max):
+    """F.scale_to_limits of every long track and the branch that decides its first round
+    ("in": within range, "v", "a"); CPU only."""
+    Ts, Cs = _long_tracks()
+    out = []
+    for T, Cf in zip(Ts, Cs):
+        pk = F.traj_peaks(T, Cf)
+        vv, av = pk[0] / v_max, pk[2] / a_max
+        branch = "in" if vv <= 1 + 1e-3 and av <= 1 + 1e-3 else "v" if vv >= np.sqrt(av) else "a"
+        out.append((F.scale_to_limits(T, Cf, v_max, a_max), branch))
+    return out
+
+
+def test_peaks_long_tracks():
+    Ts, Cs = _long_tracks()
+    assert [len(T) for T in Ts] == list(LONG_M)
+    pk, st = capi.traj_peaks(Ts, Cs)
+    _check_against_truth(Ts, Cs, pk, st)
+    # the peak of a longer prefix is never lower, and each track's is found in a batch of its own
+    assert (np.diff(pk[:, 0]) >= 0).all() and (np.diff(pk[:, 2]) >= 0).all()
+    for k in range(len(Ts)):
+        alone, ast = capi.traj_peaks(Ts[k:k + 1], Cs[k:k + 1])
+        assert ast[0] == 0 and alone[0].tobytes() == pk[k].tobytes(), k
+
+
+def test_long_tracks_take_both_scaling_branches_on_the_truth():
+    """(the inputs are what they are meant to be: on the CPU truth alone)"""
+    branches = []
+    for v_max, a_max in LIMIT_PAIRS:
+        for (_, _, _, within, rounds), branch in _long_scale_truth(v_max, a_max):
+            assert within and rounds <= 2
+            branches.append(branch)
+    print("branches", branches)
+    assert "v" in branches and "a" in branches
+
+
+@pytest.mark.parametrize("v_max,a_max", LIMIT_PAIRS)
+def test_scale_long_tracks_beside_the_ragged_set(v_max, a_max):
+    """One launch: the 1..30-segment ragged set and the long tracks, test_scale_to_limits'
+    assertions on every track."""
+    rT, rC = _ragged_fit()
+    lT, lC = _long_tracks()
+    Ts, Cs = list(rT) + list(lT), list(rC) + list(lC)
+    truth = {len(rT) + i: t for i, (t, _) in enumerate(_long_scale_truth(v_max, a_max))}
+    n_in, n_v, n_a = _check_scaling(Ts, Cs, v_max, a_max, truth)
+    long_branches = [b for _, b in _long_scale_truth(v_max, a_max)]
+    assert ("v" if (v_max, a_max) == (1.0, 2.0) else "a") in long_branches
+    assert n_v + n_a >= len(lT) - long_branches.count("in")
+
+
+def test_invalid_long_tracks_are_flagged_and_left_untouched():
+    """A NaN coefficient, a zero and an infinite segment time, each past element 255 of a
+    300-segment track: found by the second trips of track_invalid's loops."""
+    lT, lC = _long_tracks()
+    rT, rC = _ragged_fit()
+    T300, C300 = lT[-1][:300], lC[-1][:300]
+    bad = []
+    Cn = C300.copy()
+    Cn.reshape(-1)[3 * 10 * 260 + 7] = np.nan
+    bad.append((T300.copy(), Cn))
+    for i, v in ((270, 0.0), (299, np.inf)):
+        Tb = T300.copy()
+        Tb[i] = v
+        bad.append((Tb, C300.copy()))
+    good = [(lT[0], lC[0]), (rT[17], rC[17]), (T300, C300), (lT[3], lC[3])]
+    order = [good[0], bad[0], good[1], bad[1], good[2], bad[2], good[3]]
+    Ts, Cs = [t for t, _ in order], [c for _, c in order]
+    bad_at, good_at = (1, 3, 5), (0, 2, 4, 6)
+    pk, st = capi.traj_peaks(Ts, Cs)
+    Tn, Cn, sc, sst = capi.scale_to_limits(Ts, Cs, 1.0, 2.0)
+    for k in bad_at:
+        assert st[k] == -1 and np.isnan(pk[k]).all(), k
+        assert sst[k] == -1 and sc[k] == 1.0, k
+        assert Tn[k].tobytes() == Ts[k].tobytes() and Cn[k].tobytes() == Cs[k].tobytes(), k
+    # the valid neighbours: as in a launch of their own
+    gT, gC = [Ts[k] for k in good_at], [Cs[k] for k in good_at]
+    pk_g, st_g = capi.traj_peaks(gT, gC)
+    Tg, Cg, sc_g, sst_g = capi.scale_to_limits(gT, gC, 1.0, 2.0)
+    assert (st_g == 0).all() and (sst_g == 0).all() and (sc_g > 1.0).any()
+    for i, k in enumerate(good_at):
+        assert st[k] == 0 and sst[k] == 0 and pk[k].tobytes() == pk_g[i].tobytes(), k
+        assert sc[k] == sc_g[i] and Tn[k].tobytes() == Tg[i].tobytes() and Cn[k].tobytes() == Cg[i].tobytes(), k
+    _check_against_truth(gT, gC, pk_g, st_g)
+
+
+@pytest.mark.parametrize("n", [5, 9])
+def test_tie_within_a_wave_goes_to_the_earlier_segment(n):
+    """Segments s and s + 4 are searched by the same wave (4 waves stride over the segments):
+    n identical cubics tie in both peaks, within a wave and across waves; the peak times are the
+    first segment's, as test_hand_made_segments' case 2 asserts across waves."""
+    pk_single = capi.traj_peaks([[2.0]], [CUBIC])[0][0]
+    pk, st = capi.traj_peaks([[2.0] * n, [2.0]], [np.concatenate([CUBIC] * n), CUBIC])
+    print(repr(pk))
+    assert (st == 0).all()
+    assert (pk[:, 0] == pk_single[0]).all() and (pk[:, 2] == pk_single[2]).all()
+    assert (pk[:, 1] == pk_single[1]).all() and (pk[:, 3] == 0.0).all()

@@ -70,22 +70,15 @@ def _fit(name):
 
 
 def _sample(Ts, Cs, dt):
-    """(rows per track, row offsets, all rows) from epp_sample_count + epp_sample_batch."""
-    L = capi.lib()
-    nt = len(Ts)
-    d_T, d_C, d_off, _, _ = capi._upload_tracks(Ts, Cs)
-    d_cnt = capi.DeviceBuffer(8 * nt)
-    capi.check(L.epp_sample_count(d_T.ptr, d_off.ptr, nt, dt, d_cnt.ptr, None))
-    capi.sync()
-    cnt = d_cnt.download(np.int64, nt)
-    roff = np.zeros(nt + 1, np.int64)
+    """(rows per track, row offsets, all rows) from epp_sample_count + epp_sample_batch
+    (capi.sample_count / capi.sample_batch; the sampler itself is pinned by
+    test_gpu_sample_batch.py)."""
+    cnt = capi.sample_count(Ts, dt)
+    roff = np.zeros(len(Ts) + 1, np.int64)
     roff[1:] = np.cumsum(cnt)
-    total = int(roff[-1])
-    d_roff = capi.DeviceBuffer.from_array(roff[:-1].copy())
-    d_rows = capi.DeviceBuffer(80 * max(total, 1))
-    capi.check(L.epp_sample_batch(d_T.ptr, d_C.ptr, d_off.ptr, nt, dt, None, d_roff.ptr, d_rows.ptr, None))
-    capi.sync()
-    return cnt, roff, d_rows.download(np.float64, total * 10).reshape(-1, 10)
+    rows = capi.sample_batch(Ts, Cs, dt)
+    assert len(rows) == roff[-1]
+    return cnt, roff, rows
 
 
 def _compose(world, Ts, Cs, dt, md):
