@@ -233,7 +233,7 @@ struct WorldView {
     double icx, icy, icz;     // 1 / coarse cell size
     float ofx, ofy, ofz;      // grid origin rounded to float
     float i4x, i4y, i4z;      // 4 / coarse cell size, as float (fine-index scale)
-    float limx, limy, limz;   // ~4n: fine coordinates beyond are outside every AABB
+    float limx, limy, limz;   // >= fine_coord(g1): fine coordinates beyond are outside every AABB
     float fmaxx, fmaxy, fmaxz; // 4 * n - 1: largest fine index
     double r_gate, r_obst;    // inflate radii (src/World.cpp:89-90)
     // fine cell classes (k_states fast path)
@@ -350,8 +350,12 @@ struct HostWorld {
 // Fine (sub-cell) coordinate along one axis, computed in float with the same
 // operations on host and device.  Every step is monotone in p, so the candidate lists
 // and occupancy masks built from AABB corners are exact supersets of the rtree query
-// results without any rounding slack.  A point strictly inside an AABB has
-// 0 <= f <= 4n(1 + 3 * 2^-24) < lim; the fine index is F = min((int)f, 4n-1), coarse = F >> 2.
+// results without any rounding slack.  A point inside an AABB (g0 <= p <= g1) has
+// 0 = fine_coord(g0) <= f <= fine_coord(g1) <= lim, again by monotonicity: lim is computed
+// with this function (world_index.cpp).  f is NOT bounded by 4n (1 + a few ulps): the float
+// extent (float)g1 - (float)g0 differs from g1 - g0 by up to an ulp of |g0| and |g1|, which
+// far from the origin is many ulps of the extent (parts in 1e4 of 4n at 100 km).  The fine
+// index is F = min((int)f, 4n-1), coarse = F >> 2.
 #if defined(__HIPCC__)
 __host__ __device__
 #endif

@@ -175,10 +175,15 @@ bool build_blob(HostWorld& hw, const epp_obb* obbs, int n) {
     const float i4[3] = {(float)(4.0 * inv[0]), (float)(4.0 * inv[1]), (float)(4.0 * inv[2])};
     v.ofx = of[0]; v.ofy = of[1]; v.ofz = of[2];
     v.i4x = i4[0]; v.i4y = i4[1]; v.i4z = i4[2];
-    // fine coordinate of any point strictly inside an AABB is <= 4n (1 + 3 * 2^-24)
-    v.limx = (float)(4 * nd[0]) * (1.0f + 0x1.0p-20f);
-    v.limy = (float)(4 * nd[1]) * (1.0f + 0x1.0p-20f);
-    v.limz = (float)(4 * nd[2]) * (1.0f + 0x1.0p-20f);
+    // The upper cut of the cull: the fine coordinate of g1 itself, by the function the kernels
+    // use.  fine_coord is monotone in p, so no point inside an AABB (p <= g1) lies beyond it.
+    // (It is about 4n, but only to within ulps of |g0| and |g1| over the extent: the float
+    // extent (float)g1 - (float)g0 is that far off far from the origin.)  Never below
+    // 4n (1 + 2^-20), the cut of earlier versions.
+    float lim[3];
+    for (int k = 0; k < 3; ++k)
+        lim[k] = std::max((float)(4 * nd[k]) * (1.0f + 0x1.0p-20f), fine_coord(g1[k], of[k], i4[k]));
+    v.limx = lim[0]; v.limy = lim[1]; v.limz = lim[2];
     v.fmaxx = (float)(4 * nd[0] - 1); v.fmaxy = (float)(4 * nd[1] - 1); v.fmaxz = (float)(4 * nd[2] - 1);
     const int ncell = nd[0] * nd[1] * nd[2];
     std::vector<uint64_t> mask(ncell, 0);
@@ -921,6 +926,22 @@ extern "C" epp_status epp_dbg_class_layout(const epp_obb* obbs, int32_t n, doubl
                               (int64_t)((v.off_cls8 ? ((v.off_cls8 + v.cls8_bytes + 15u) & ~15u) : v.blob_bytes) -
                                         v.off_pt)};
     for (int k = 0; k < 12; ++k) out[k] = vals[k];
+    return EPP_OK;
+}
+
+// Debug entry (not part of include/epp.h): the cull grid of a world's index, host build only.
+// out: nx, ny, nz, ofx..z, i4x..z, limx..z, fmaxx..z (the floats as doubles), g0[3], g1[3].
+extern "C" epp_status epp_dbg_cull_grid(const epp_obb* obbs, int32_t n, double r_gate, double r_obst, double out[21]) {
+    if (!out || n < 0 || (n > 0 && !obbs)) return EPP_ERR_INVALID_ARGUMENT;
+    epp::HostWorld hw;
+    hw.r_gate = r_gate;
+    hw.r_obst = r_obst;
+    if (!epp::build_blob(hw, obbs, n)) return EPP_ERR_UNSUPPORTED;
+    const epp::WorldView& v = hw.view;
+    const double vals[21] = {(double)v.nx, (double)v.ny, (double)v.nz, v.ofx, v.ofy, v.ofz, v.i4x, v.i4y, v.i4z,
+                             v.limx, v.limy, v.limz, v.fmaxx, v.fmaxy, v.fmaxz, v.gx0, v.gy0, v.gz0,
+                             v.gx1, v.gy1, v.gz1};
+    for (int k = 0; k < 21; ++k) out[k] = vals[k];
     return EPP_OK;
 }
 
