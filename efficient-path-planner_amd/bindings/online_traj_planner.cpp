@@ -328,6 +328,33 @@ PYBIND11_MODULE(online_traj_planner, m) {
             py::arg("waypoint_sets"), py::arg("v_max"), py::arg("a_max"), py::arg("sampling_interval"),
             py::arg("frames"), py::arg("half_edge") = 0.425)
         .def(
+            "candidate_thrust_rates",  // fit + thrust / body rate / tilt extremes of K waypoint sets (this build)
+            [](const epp::PathPlanner& self, const std::vector<py::object>& waypointSets, double vMax, double aMax,
+               double samplingInterval, double g) {
+                std::vector<std::vector<Vec3>> sets;
+                for (const auto& o : waypointSets) {
+                    Matrix w = to_matrix(o);
+                    if (w.cols != 3) throw std::invalid_argument("waypoints must be an (n, 3) array");
+                    std::vector<Vec3> wp;
+                    for (size_t i = 0; i < w.rows; ++i) wp.emplace_back(w(i, 0), w(i, 1), w(i, 2));
+                    sets.push_back(std::move(wp));
+                }
+                std::vector<double> out;
+                std::vector<long> rows;
+                {
+                    py::gil_scoped_release release;
+                    self.candidateThrustRates(sets, vMax, aMax, samplingInterval, g, out, &rows);
+                }
+                const py::ssize_t K = (py::ssize_t)sets.size();
+                py::array_t<double> o({K, (py::ssize_t)8});
+                py::array_t<int64_t> r({K, (py::ssize_t)4});
+                for (size_t i = 0; i < out.size(); ++i) o.mutable_data()[i] = out[i];
+                for (size_t i = 0; i < rows.size(); ++i) r.mutable_data()[i] = rows[i];
+                return py::make_tuple(o, r);
+            },
+            py::arg("waypoint_sets"), py::arg("v_max"), py::arg("a_max"), py::arg("sampling_interval"),
+            py::arg("g") = 9.81)
+        .def(
             "first_hits",  // where every edge s1[i] -> s2[i] is first blocked, and by which OBB (this build)
             [](const epp::PathPlanner& self, const py::object& s1, const py::object& s2, bool canPassGate) {
                 Matrix a = to_matrix(s1), b = to_matrix(s2);

@@ -99,7 +99,9 @@ namespace {
 // and the hit's time into rowTimes.  gp != nullptr: instead of the checks, the ordered gate
 // passage of every fitted track (epp_traj_gate_pass_batch) against gp's frame table, uploaded
 // with the waypoints; its n x G outputs take a part of the device block of their own.  Gates
-// are no OBBs: no world takes part.
+// are no OBBs: no world takes part.  tr != nullptr: instead of the checks, the extremes of thrust,
+// body rate and tilt of every fitted track's rows (epp_traj_thrust_rates_batch) into tr's n x 8
+// and n x 4 outputs, which take a part of the device block of their own; no world takes part.
 struct CandidateClear {
     std::vector<double>& clearance;
     std::vector<int>* nearest;
@@ -116,12 +118,17 @@ struct CandidateGates {
     std::vector<int>& nPassed;  // n
     std::vector<double>* offsets;  // n x G x 2
 };
+struct CandidateThrust {
+    double g;
+    std::vector<double>& out;  // n x 8
+    std::vector<long>* rows;   // n x 4
+};
 void fit_and_check_candidates(const char* what, const epp_world* world, const std::vector<std::vector<Vec3>>& sets,
                               double v_max, double a_max, double dt, double minDistance, int32_t canPassGate,
                               std::vector<long>& firstInvalidRow, std::vector<double>* rowTimes,
                               std::vector<long>* chords, std::vector<double>* chordTimes,
                               const CandidateClear* clr = nullptr, const CandidateHit* hit = nullptr,
-                              const CandidateGates* gp = nullptr) {
+                              const CandidateGates* gp = nullptr, const CandidateThrust* tr = nullptr) {
     if (gp && (gp->frames.cols != 5 || gp->frames.rows > 64))
         throw std::invalid_argument(std::string(what) + ": the gate frame table must be (G <= 64) x 5");
     for (const auto& s : sets)
@@ -146,9 +153,17 @@ void fit_and_check_candidates(const char* what, const epp_world* world, const st
         gp->nPassed.assign(n, 0);
         if (gp->offsets) gp->offsets->assign(n * G * 2, NAN);
     }
+    if (tr) {
+        tr->out.resize(n * 8);
+        for (size_t k = 0; k < n; ++k) {
+            const double identity[8] = {HUGE_VAL, -1.0, -HUGE_VAL, -1.0, -HUGE_VAL, -1.0, HUGE_VAL, -1.0};
+            std::copy(identity, identity + 8, tr->out.begin() + 8 * k);
+        }
+        if (tr->rows) tr->rows->assign(n * 4, -1);
+    }
     if (n == 0) return;
     // host image of the upload: [waypoints | offsets]; device block: [wp | T | coeffs |
-    // first_time | first_invalid | chord_time | chord | offsets | status]
+    // first_time | first_invalid | chord_time | chord | offsets | status | gate parts | thrust parts]
     size_t total = 0;
     for (const auto& s : sets) total += s.size();
     const size_t nseg = total - n;
@@ -181,7 +196,8 @@ void fit_and_check_candidates(const char* what, const epp_world* world, const st
                  o_fi = after(o_ft, n * 8), o_ct = after(o_fi, n * 8), o_ci = after(o_ct, n * 8),
                  o_off = after(o_ci, n * 8), o_st = after(o_off, (n + 1) * 4), o_gf = after(o_st, n * 4),
                  o_gc = after(o_gf, G * 40), o_gt = after(o_gc, n * G * 8), o_go = after(o_gt, n * G * 8),
-                 o_gn = after(o_go, n * G * 16), bytes = after(o_gn, gp ? n * 4 : 0);
+                 o_gn = after(o_go, n * G * 16), o_to = after(o_gn, gp ? n * 4 : 0),
+                 o_tr = after(o_to, tr ? n * 64 : 0), bytes = after(o_tr, tr ? n * 32 : 0);
     need(epp_malloc(&d.buf, bytes));
     need(epp_stream_create(&d.st));
     char* base = static_cast<char*>(d.buf);
@@ -199,6 +215,9 @@ void fit_and_check_candidates(const char* what, const epp_world* world, const st
                                       reinterpret_cast<double*>(base + o_gt),
                                       gp->offsets ? reinterpret_cast<double*>(base + o_go) : nullptr,
                                       reinterpret_cast<int32_t*>(base + o_gn), d.st));
+    else if (tr)
+        need(epp_traj_thrust_rates_batch(d_T, d_C, d_off, (int32_t)n, dt, tr->g, reinterpret_cast<double*>(base + o_to),
+                                         tr->rows ? reinterpret_cast<int64_t*>(base + o_tr) : nullptr, d.st));
     else if (clr)  // (the chord slots hold the clearance and the nearest OBB)
         need(epp_traj_clearance_batch(world, d_T, d_C, d_off, (int32_t)n, dt, reinterpret_cast<double*>(base + o_ct),
                                       reinterpret_cast<int64_t*>(base + o_fi), reinterpret_cast<double*>(base + o_ft),
@@ -220,7 +239,7 @@ void fit_and_check_candidates(const char* what, const epp_world* world, const st
     std::vector<int64_t> rows(n), crows(n);
     std::vector<double> times(n), ctimes(n);
     need(epp_memcpy_d2h_async(status.data(), base + o_st, n * 4, d.st));
-    if (!gp) {
+    if (!gp && !tr) {
         need(epp_memcpy_d2h_async(rows.data(), base + o_fi, n * 8, d.st));
         need(epp_memcpy_d2h_async(times.data(), base + o_ft, n * 8, d.st));
     }
@@ -233,6 +252,12 @@ void fit_and_check_candidates(const char* what, const epp_world* world, const st
             need(epp_memcpy_d2h_async(gp->time.data(), base + o_gt, n * G * 8, d.st));
             if (gp->offsets) need(epp_memcpy_d2h_async(gp->offsets->data(), base + o_go, n * G * 16, d.st));
         }
+    }
+    std::vector<int64_t> trows(tr && tr->rows ? n * 4 : 0);
+    std::vector<double> tout(tr ? n * 8 : 0);  // (tr->out keeps the identities if the call throws)
+    if (tr) {
+        need(epp_memcpy_d2h_async(tout.data(), base + o_to, n * 64, d.st));
+        if (tr->rows) need(epp_memcpy_d2h_async(trows.data(), base + o_tr, n * 32, d.st));
     }
     if (chords) {
         need(epp_memcpy_d2h_async(crows.data(), base + o_ci, n * 8, d.st));
@@ -260,6 +285,8 @@ void fit_and_check_candidates(const char* what, const epp_world* world, const st
         gp->chord.assign(gchord.begin(), gchord.end());
         gp->nPassed.assign(gpassed.begin(), gpassed.end());
     }
+    if (tr) tr->out = tout;
+    if (tr && tr->rows) tr->rows->assign(trows.begin(), trows.end());
 }
 }  // namespace
 
@@ -297,6 +324,14 @@ void PathPlanner::candidateGatePasses(const std::vector<std::vector<Vec3>>& sets
     const CandidateGates gp{frames, halfEdge, chord, time, nPassed, offsets};
     fit_and_check_candidates("candidateGatePasses", nullptr, sets, v_max, a_max, dt, 0.0, 0, rows, nullptr, nullptr,
                              nullptr, nullptr, nullptr, &gp);
+}
+
+void PathPlanner::candidateThrustRates(const std::vector<std::vector<Vec3>>& sets, double v_max, double a_max,
+                                       double dt, double g, std::vector<double>& out, std::vector<long>* rows) const {
+    std::vector<long> none;
+    const CandidateThrust tr{g, out, rows};
+    fit_and_check_candidates("candidateThrustRates", nullptr, sets, v_max, a_max, dt, 0.0, 0, none, nullptr, nullptr,
+                             nullptr, nullptr, nullptr, nullptr, &tr);
 }
 
 void PathPlanner::candidateClearances(const std::vector<std::vector<Vec3>>& sets, double v_max, double a_max, double dt,

@@ -819,21 +819,13 @@ epp_status ensure_consts() {
     int dev = 0;
     (void)hipGetDevice(&dev);
     if (dev >= 0 && dev < 64 && g_consts_ready[dev]) return EPP_OK;
-    double B[N][N];
-    std::memset(B, 0, sizeof(B));
-    for (int i = 0; i < N; ++i) B[0][i] = 1.0;
-    int order = N - 1;
-    for (int n = 1; n < N; ++n) {
-        for (int i = N - 1 - order; i < N; ++i) B[n][i] = (order - (N - 1) + i) * B[n - 1][i];
-        order--;
-    }
     // B5^-1, K (the closed-form mapping inverse, ainv_entry) and Hc (see hess): exact
     // rationals rounded once to double (minsnap_consts.h, scripts/gen_minsnap_consts.py).
     // (Round 5 derived them here in long double; Hc's products cancel, and some entries
     // were ~3e-13 off -- data error the solve amplified to ~1e-9 in the coefficients.)
     double cc[kNC] = {};
     for (int k = 0; k < N; ++k)
-        for (int j = 0; j < N; ++j) cc[kCB + k * N + j] = B[k][j];
+        for (int j = 0; j < N; ++j) cc[kCB + k * N + j] = falling_factorial(k, j);  // (traj_sample.h)
     for (int r = 0; r < HALF; ++r)
         for (int c = 0; c < HALF; ++c) {
             cc[kCB5 + r * HALF + c] = minsnap_consts::kB5inv[r * HALF + c];

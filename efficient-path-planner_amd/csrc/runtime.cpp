@@ -81,6 +81,12 @@ epp_status epp_set_device(int device) {
     EPP_HIP_RET(hipSetDevice(device));
     return EPP_OK;
 }
+epp_status epp_device_cu_count(int* count) {
+    int d = 0;
+    EPP_HIP_RET(hipGetDevice(&d));
+    EPP_HIP_RET(hipDeviceGetAttribute(count, hipDeviceAttributeMultiprocessorCount, d));
+    return EPP_OK;
+}
 epp_status epp_malloc(void** ptr, uint64_t bytes) {
     EPP_HIP_RET(hipMalloc(ptr, bytes ? bytes : 16));
     return EPP_OK;

@@ -2,10 +2,10 @@
 // recurrence (RangeIter), the one loop that steps it (range_produce / range_count) and the
 // polynomial evaluation.  Everything that samples a track runs these: the row sampler
 // (minsnap.hip: k_sample_count, k_sample_rows, the host recurrences of the single-track
-// paths), the fused checks (trajcheck.hip: k_traj_check, k_traj_sweep) and
-// tests/traj_rows_host.cpp.  One definition, so all produce the same sample times, segments
-// and positions bit for bit.  Plain C++ apart from the HIP qualifiers: a host program may
-// include it without the HIP runtime.
+// paths), the fused checks (trajcheck.hip: k_traj_check, k_traj_sweep), the derivative sampler
+// and the thrust / rate walk (thrust_rates.hip) and tests/traj_rows_host.cpp.  One definition,
+// so all produce the same sample times, segments and positions bit for bit.  Plain C++ apart
+// from the HIP qualifiers: a host program may include it without the HIP runtime.
 #pragma once
 
 #if defined(__HIPCC__)
@@ -143,6 +143,28 @@ EPP_TS_FN double poly_eval(const double* B, const double* c, double t, int k) {
     constexpr int N = kPolyCoeffs;
     double r = B[k * N + N - 1] * c[N - 1];
     for (int j = N - 2; j >= k; --j) r = fma(r, t, B[k * N + j] * c[j]);
+    return r;
+}
+
+// B[k][j] = j! / (j-k)! itself (0 for j < k): an exact small integer (at most 9! = 362880),
+// so a table filled from here, or a product with it, has the bits of the staged table's.
+EPP_TS_FN constexpr double falling_factorial(int k, int j) {
+    int f = j >= k ? 1 : 0;
+    for (int i = 0; i < k; ++i) f *= j - i;
+    return (double)f;
+}
+
+// poly_eval(B, c, t, K) for a compile-time K, without the table: the same products
+// B[K][j] * c[j], each rounded once, and the same fused Horner steps, so the same bits
+// (tests/test_gpu_thrust_rates.py compares them through the fused thrust / rate call).
+template <int K>
+EPP_TS_FN double poly_eval_order(const double* c, double t) {
+    constexpr int N = kPolyCoeffs;
+    double r = falling_factorial(K, N - 1) * c[N - 1];
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int j = N - 2; j >= K; --j) r = fma(r, t, falling_factorial(K, j) * c[j]);
     return r;
 }
 

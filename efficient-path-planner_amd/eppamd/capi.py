@@ -48,6 +48,7 @@ def lib() -> C.CDLL:
             "epp_version": (C.c_char_p, []),
             "epp_device_count": (i32, [C.POINTER(C.c_int)]),
             "epp_set_device": (i32, [C.c_int]),
+            "epp_device_cu_count": (i32, [C.POINTER(C.c_int)]),
             "epp_malloc": (i32, [C.POINTER(vp), u64]),
             "epp_free": (i32, [vp]),
             "epp_memcpy_h2d": (i32, [vp, vp, u64, vp]),
@@ -103,6 +104,9 @@ def lib() -> C.CDLL:
             "epp_traj_first_hit_batch": (i32, [vp, vp, vp, vp, i32, dp, i32, vp, vp, vp, vp, vp]),
             "epp_gates_crossed": (i32, [vp, i32, dp, vp, vp, i64, vp, vp]),
             "epp_traj_gate_pass_batch": (i32, [vp, i32, dp, vp, vp, vp, i32, dp, vp, vp, vp, vp, vp]),
+            "epp_sample_derivative_batch": (i32, [vp, vp, vp, i32, dp, i32, vp, vp, vp]),
+            "epp_thrust_rates": (i32, [vp, vp, i64, dp, vp, vp, vp, vp]),
+            "epp_traj_thrust_rates_batch": (i32, [vp, vp, vp, i32, dp, dp, vp, vp, vp]),
             "epp_generate_trajectory_limited_host": (i32, [vp, i32, dp, dp, dp, dp, vp, vp,
                                                            C.POINTER(C.POINTER(C.c_double)), C.POINTER(i64),
                                                            C.POINTER(C.c_double)]),
@@ -168,6 +172,7 @@ EXPORTED = [
     "epp_traj_peaks", "epp_traj_scale_to_limits", "epp_generate_trajectory_limited_host",
     "epp_traj_check_batch", "epp_traj_sweep_batch", "epp_states_clearance", "epp_traj_clearance_batch",
     "epp_motions_first_hit", "epp_traj_first_hit_batch", "epp_gates_crossed", "epp_traj_gate_pass_batch",
+    "epp_sample_derivative_batch", "epp_thrust_rates", "epp_traj_thrust_rates_batch", "epp_device_cu_count",
 ]
 
 
@@ -225,6 +230,13 @@ class DeviceBuffer:
 def device_count() -> int:
     n = C.c_int(0)
     check(lib().epp_device_count(C.byref(n)))
+    return n.value
+
+
+def cu_count() -> int:
+    """The compute units of the current device (epp_device_cu_count)."""
+    n = C.c_int(0)
+    check(lib().epp_device_cu_count(C.byref(n)))
     return n.value
 
 
@@ -634,6 +646,59 @@ def trajectory_gate_passes(frames, half_edge: float, Ts, Cs, dt: float):
     sync()
     return (d_chord.download(np.int64, nt * G).reshape(nt, G), d_time.download(np.float64, nt * G).reshape(nt, G),
             d_o.download(np.float64, nt * G * 2).reshape(nt, G, 2), d_np.download(np.int32, nt))
+
+
+GRAVITY = 9.81  # m/s^2: the default g of thrust_rates / trajectory_thrust_rates
+
+
+def sample_derivative(Ts, Cs, dt: float, order: int):
+    """epp_sample_derivative_batch on the lists minsnap_batch returns: derivative `order`
+    (0..9) of every row of every track, [x, y, z]; the tracks' rows follow each other (the
+    exclusive scan of sample_count).  Returns (float64[n_rows, 3], int64[n + 1] row offsets)."""
+    nt = len(Ts)
+    dt = float(dt)
+    d_T, d_C, d_off, _, _ = _upload_tracks(Ts, Cs)
+    roff = np.zeros(nt + 1, np.int64)
+    if nt:
+        d_cnt = DeviceBuffer(8 * nt)
+        check(lib().epp_sample_count(d_T.ptr, d_off.ptr, nt, dt, d_cnt.ptr, None))
+        sync()
+        roff[1:] = np.cumsum(d_cnt.download(np.int64, nt))
+    n_rows = int(roff[-1])
+    d_val = _filled(24 * max(n_rows, 1), None)
+    d_roff = DeviceBuffer.from_array(roff)
+    check(lib().epp_sample_derivative_batch(d_T.ptr, d_C.ptr, d_off.ptr, nt, dt, int(order), d_roff.ptr, d_val.ptr,
+                                            None))
+    sync()
+    return d_val.download(np.float64, n_rows * 3).reshape(n_rows, 3), roff
+
+
+def thrust_rates(acc, jerk, g: float = GRAVITY):
+    """epp_thrust_rates: per sample, from its acceleration and jerk (n x 3 each), the
+    mass-normalised thrust |a + g e_z|, the roll / pitch body rate |F x j| / |F|^2 and the
+    cosine of the tilt F_z / |F|.  Returns (float64[n], float64[n], float64[n])."""
+    acc = np.ascontiguousarray(acc, np.float64).reshape(-1, 3)
+    jerk = np.ascontiguousarray(jerk, np.float64).reshape(-1, 3)
+    n = len(acc)
+    assert len(jerk) == n
+    d_a, d_j = DeviceBuffer.from_array(acc), DeviceBuffer.from_array(jerk)
+    d_f, d_r, d_c = DeviceBuffer(8 * n), DeviceBuffer(8 * n), DeviceBuffer(8 * n)
+    check(lib().epp_thrust_rates(d_a.ptr, d_j.ptr, n, float(g), d_f.ptr, d_r.ptr, d_c.ptr, None))
+    sync()
+    return d_f.download(np.float64, n), d_r.download(np.float64, n), d_c.download(np.float64, n)
+
+
+def trajectory_thrust_rates(Ts, Cs, dt: float, g: float = GRAVITY):
+    """epp_traj_thrust_rates_batch on the lists minsnap_batch returns: per track [f_min,
+    t_fmin, f_max, t_fmax, rate_max, t_rate, cos_min, t_cos] over its rows at dt and the four
+    rows that attain them (-1: none).  Returns (float64[n, 8], int64[n, 4])."""
+    nt = len(Ts)
+    d_T, d_C, d_off, _, _ = _upload_tracks(Ts, Cs)
+    d_out, d_rows = DeviceBuffer(64 * nt), DeviceBuffer(32 * nt)
+    check(lib().epp_traj_thrust_rates_batch(d_T.ptr, d_C.ptr, d_off.ptr, nt, float(dt), float(g), d_out.ptr,
+                                            d_rows.ptr, None))
+    sync()
+    return d_out.download(np.float64, 8 * nt).reshape(nt, 8), d_rows.download(np.int64, 4 * nt).reshape(nt, 4)
 
 
 def traj_peaks(Ts, Cs):

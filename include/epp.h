@@ -45,6 +45,12 @@
  *   epp_gates_crossed / epp_traj_gate_pass_batch
  *       OnlineTrajGenerator::checkGatePassed (src/OnlineTrajGenerator.cpp:228-256), per edge
  *       and gate, and as the ordered passage of every fitted track's chords with split times.
+ *   epp_sample_derivative_batch
+ *       Trajectory::evaluateRange(t_start, t_end, dt, derivative_order, ...)
+ *       (external/poly_traj/src/trajectory.cpp:81-141) for any derivative, batched over tracks.
+ *   epp_thrust_rates / epp_traj_thrust_rates_batch
+ *       no reference counterpart: the thrust, the roll / pitch body rate and the tilt a
+ *       quadrotor needs at a sample, and their extremes over every fitted track's rows.
  */
 #ifndef EPP_H_
 #define EPP_H_
@@ -93,6 +99,9 @@ const char* epp_last_error(void);
 const char* epp_version(void);
 epp_status epp_device_count(int* count);
 epp_status epp_set_device(int device);
+/* The compute units of the current device (the number the persistent grids of the k_traj_*
+ * kernels are sized by: at most 8 workgroups per compute unit). */
+epp_status epp_device_cu_count(int* count);
 epp_status epp_malloc(void** ptr, uint64_t bytes);
 epp_status epp_free(void* ptr);
 epp_status epp_memcpy_h2d(void* dst, const void* src, uint64_t bytes, void* stream);
@@ -408,6 +417,63 @@ epp_status epp_gates_crossed(const double* gates, int32_t n_gates, double half_e
 epp_status epp_traj_gate_pass_batch(const double* gates, int32_t n_gates, double half_edge, const double* seg_times,
                                     const double* coeffs, const int32_t* wp_offsets, int32_t n_tracks, double dt,
                                     int64_t* chord, double* time, double* offset, int32_t* n_passed, void* stream);
+
+/* ---- thrust and body rates: what a quadrotor must do to fly a fitted track (device pointers).
+ * No epp_world takes part.  The input-feasibility quantities of a differentially flat quadrotor
+ * track (Mueller, Hehn, D'Andrea 2015) need the acceleration and the jerk of its rows. */
+/* Trajectory::evaluateRange(0, max_time, dt, order) (external/poly_traj/src/trajectory.cpp:
+ * 81-141) for every track of a batch in the layout of epp_minsnap_batch: values (total rows x 3
+ * f64, [x, y, z]) holds derivative `order` (0..9) of every row; track k is written from row
+ * row_offsets[k] on (device int64; a NULL row_offsets: every track from row 0, for one track).
+ * The rows are those of epp_sample_count / epp_sample_batch (the same recurrence), and each
+ * value is the sampler's own evaluation: the products B[order][j] * c_j rounded once each, then
+ * fused Horner steps; so for order 0, 1, 2 the values equal columns 3 d + order of
+ * epp_sample_batch's rows bit for bit.  A track without rows (one waypoint, the NaN times of a
+ * failed fit) writes nothing.  Stream-ordered, no host synchronisation and no allocation, so
+ * the call can be captured (epp_graph_begin).  EPP_ERR_INVALID_ARGUMENT (before any device
+ * work) for order outside 0..9, n_tracks < 0, dt <= 0 or not finite, or a NULL seg_times,
+ * coeffs, wp_offsets or values with n_tracks > 0; n_tracks == 0 launches nothing. */
+epp_status epp_sample_derivative_batch(const double* seg_times, const double* coeffs, const int32_t* wp_offsets,
+                                       int32_t n_tracks, double dt, int32_t order, const int64_t* row_offsets,
+                                       double* values, void* stream);
+/* Per sample, from its acceleration a and jerk j (acc, jerk: n x 3 f64 each) and the gravity g,
+ * every operation one IEEE fp64 multiply, add, subtract, divide or square root in this
+ * association, nothing fused:
+ *   Fx = ax;  Fy = ay;  Fz = az + g                      (mass-normalised thrust vector)
+ *   f2 = (Fx*Fx + Fy*Fy) + Fz*Fz;       thrust   = sqrt(f2)
+ *   cx = Fy*jz - Fz*jy;  cy = Fz*jx - Fx*jz;  cz = Fx*jy - Fy*jx
+ *   w2 = (cx*cx + cy*cy) + cz*cz;       rate     = sqrt(w2) / f2
+ *                                       cos_tilt = Fz / thrust
+ * rate = |F x j| / |F|^2 is the angular rate of the thrust direction: the roll / pitch body
+ * rate.  No trigonometric function is called: the tilt angle is acos(cos_tilt).  At f2 == 0
+ * (free fall) thrust is 0, cos_tilt NaN and rate NaN or +inf, as the operations give;
+ * non-finite inputs go through the same operations and nothing more is promised for them.
+ * thrust, rate, cos_tilt: n device f64 each; rate and cos_tilt may be NULL.  Stream-ordered, no
+ * host synchronisation and no allocation, so the call can be captured (epp_graph_begin).
+ * EPP_ERR_INVALID_ARGUMENT (before any device work) for n < 0, a non-finite g, or a NULL acc,
+ * jerk or thrust with n > 0; n == 0 launches nothing. */
+epp_status epp_thrust_rates(const double* acc, const double* jerk, int64_t n, double g, double* thrust, double* rate,
+                            double* cos_tilt, void* stream);
+/* The extremes of the three quantities over every track of a batch in the layout of
+ * epp_minsnap_batch, straight from the coefficients, in one launch and without writing a row.
+ * Over the rows of Trajectory::evaluateRange(0, max_time, dt) of track k, with a and j the
+ * order-2 and order-3 values epp_sample_derivative_batch gives:
+ *   out[k * 8 + ..] (device f64) = [f_min, t_fmin, f_max, t_fmax, rate_max, t_rate, cos_min, t_cos]
+ *   rows[k * 4 + ..] (device int64, may be NULL) = the rows of f_min, f_max, rate_max, cos_min
+ * Each extreme is taken over the row values themselves (the rounded thrust, rate, cos_tilt),
+ * the earliest row that attains it wins, and a value replaces the running extreme only on
+ * strict < or >: a NaN never does, a +inf rate does.  Each t_* is that row's time column as
+ * epp_sample_batch writes it with t0 == NULL.  A track without rows (one waypoint, the NaN
+ * times of a failed fit) and a quantity that is NaN on every row keep the reductions'
+ * identities [+inf, -1, -inf, -1, -inf, -1, +inf, -1] and row -1.  The answers are those of
+ * epp_sample_count + epp_sample_batch (the time column), epp_sample_derivative_batch at orders
+ * 2 and 3, epp_thrust_rates on those values and the per-track reductions, bit for bit.
+ * Stream-ordered, no host synchronisation and no allocation, so the call can be captured.
+ * EPP_ERR_INVALID_ARGUMENT (before any device work) as epp_sample_derivative_batch, for a
+ * non-finite g, or a NULL out with n_tracks > 0; n_tracks == 0 launches nothing. */
+epp_status epp_traj_thrust_rates_batch(const double* seg_times, const double* coeffs, const int32_t* wp_offsets,
+                                       int32_t n_tracks, double dt, double g, double* out, int64_t* rows,
+                                       void* stream);
 
 /* ---- batch planner building blocks (device pointers) ------------------------------- */
 /* Replace OMPL's sampler / nearest-neighbour structure behind PathPlanner::planPath

@@ -175,6 +175,18 @@ public:
                              const Matrix& frames, double halfEdge, std::vector<long>& chord,
                              std::vector<double>& time, std::vector<int>& nPassed,
                              std::vector<double>* offsets = nullptr) const;
+    // What a quadrotor must do to fly each of K candidate waypoint sets' trajectories (an
+    // addition of this build), to rank candidates after validity: the fit of every set as
+    // above and, on the same stream with one synchronisation, epp_traj_thrust_rates_batch
+    // (include/epp.h) of the fits' rows at dt under the gravity g.  Row-major K x 8:
+    // out[k * 8 + ..] = [f_min, t_fmin, f_max, t_fmax, rate_max, t_rate, cos_min, t_cos]: the
+    // extremes over set k's rows of the mass-normalised thrust |a + g e_z|, the roll / pitch
+    // body rate |F x j| / |F|^2 and the cosine of the tilt, each with its row's time; rows
+    // (optional, K x 4): the earliest rows that attain them, -1 for a quantity that is NaN on
+    // every row (its value then +inf for a minimum, -inf for a maximum).  Throws as
+    // checkCandidateTrajectories.
+    void candidateThrustRates(const std::vector<std::vector<Vec3>>& waypointSets, double v_max, double a_max, double dt,
+                              double g, std::vector<double>& out, std::vector<long>* rows = nullptr) const;
     std::vector<Vec3> includeGates2(std::vector<std::vector<Vec3>> waypoints) const;
     // planPaths of consecutive gate-to-gate segments, then includeGates2 of their paths (an
     // addition of this build, for OnlineTrajGenerator::preComputeTraj): the same answers as
