@@ -158,6 +158,12 @@ __device__ __forceinline__ void knn_scan_block(const KnnGrid* __restrict__ gp, c
     }
 }
 
+// An empty slot of a top-K list is (r2max, kKnnNone): the index below every node's, so a
+// candidate at exactly the radius loses the tie against it and knn_insert keeps the one
+// radius rule of every k-NN path -- in range iff d < max_dist^2 (epp.h).  It is also what
+// the table holds for a missing neighbour, so the rows are stored as they are.
+constexpr int kKnnNone = -1;
+
 // Insert candidate (d, j) into the sorted top-K (distance, then index): ties keep the
 // lower index first, so the visiting order never changes the result.  Branch-free: the
 // entries ahead of (d, j) form a prefix of the list; each slot keeps its entry, takes
@@ -253,7 +259,7 @@ __device__ void knn_walk(const KnnGrid& g, const int (&c)[3], const double (&p)[
 template <int K>
 __device__ __forceinline__ void knn_store(int32_t* __restrict__ nbr, int self, const int (&bi)[K]) {
 #pragma unroll
-    for (int k = 0; k < K; ++k) nbr[(int64_t)self * K + k] = bi[k] == 0x7fffffff ? -1 : bi[k];
+    for (int k = 0; k < K; ++k) nbr[(int64_t)self * K + k] = bi[k];  // (kKnnNone = -1: a missing neighbour)
 }
 
 // Scratch of the grid k-NN, every part 256-byte aligned: grid params | bounds partials | cell_of[n] |

@@ -26,7 +26,10 @@ constexpr double kNodesPerCell = 1.5;  // mean nodes per grid cell (EPP_KNN_NPC 
 // k_knn_tile's blocks of kTileB^3 cells and their kTileH-cell halos (k_knn_retry starts past them)
 constexpr int kTileB = 4, kTileH = 2, kTileE = kTileB + 2 * kTileH, kTileCells = kTileE * kTileE * kTileE;
 
-// The squared search radius the kernels take (none: every node is in range).
+// The squared search radius the kernels take (none: every node is in range).  One rule on every
+// path: a neighbour is in range iff its squared distance is < r2max, exclusive -- k_knn's strict
+// compare against the empty slots' r2max, the retry's ranked lists, and knn_insert's tie against
+// an empty slot (r2max, kKnnNone), which a candidate at exactly the radius loses.
 inline double knn_r2max(double max_dist) { return max_dist > 0 ? max_dist * max_dist : 1e300; }
 
 // f(std::integral_constant<int, K>) for the runtime k: K = 4, 8 or 16, or 32 where the kernel

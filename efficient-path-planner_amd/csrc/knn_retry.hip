@@ -156,7 +156,7 @@ __device__ __forceinline__ void knn_retry_wave(const KnnGrid& g, double r2max, c
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         bd[k] = r2max;
-        bi[k] = 0x7fffffff;
+        bi[k] = kKnnNone;
     }
     // candidates of cells [xa, xb] of row (y, z) into the lane's list
     auto scan = [&](int y, int z, int xa, int xb) {
@@ -212,7 +212,7 @@ __device__ __forceinline__ void knn_retry_wave(const KnnGrid& g, double r2max, c
         if (bound != INFINITY && R < rmax && !(r2max < bound)) {  // (radius below it: done)
             int below = 0;
 #pragma unroll
-            for (int k = 0; k < K; ++k) below += (bi[k] != 0x7fffffff && bd[k] < bound) ? 1 : 0;
+            for (int k = 0; k < K; ++k) below += (bi[k] != kKnnNone && bd[k] < bound) ? 1 : 0;
             for (int o = 32; o > 0; o >>= 1) below += __shfl_xor(below, o, 64);
             if (below < K) continue;
         }
@@ -232,15 +232,15 @@ __device__ __forceinline__ void knn_retry_wave(const KnnGrid& g, double r2max, c
                 mi = oi;
             }
         }
-        if (lane == 0) nbr[(int64_t)self * K + k] = mi == 0x7fffffff ? -1 : mi;
-        if (mi != 0x7fffffff && bi[0] == mi) {  // the winning lane drops its head
+        if (lane == 0) nbr[(int64_t)self * K + k] = mi;  // (kKnnNone = -1: fewer than K)
+        if (mi != kKnnNone && bi[0] == mi) {  // the winning lane drops its head
 #pragma unroll
             for (int t = 0; t + 1 < K; ++t) {
                 bd[t] = bd[t + 1];
                 bi[t] = bi[t + 1];
             }
             bd[K - 1] = r2max;
-            bi[K - 1] = 0x7fffffff;
+            bi[K - 1] = kKnnNone;
         }
     }
 }

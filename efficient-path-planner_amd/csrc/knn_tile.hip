@@ -360,7 +360,7 @@ __global__ __launch_bounds__(kTileThreads, 3) void k_knn_tile(KnnGrid* __restric
 #pragma unroll
                     for (int k = 0; k < K; ++k) {
                         bd[k] = r2max;
-                        bi[k] = 0x7fffffff;
+                        bi[k] = kKnnNone;
                     }
                     // exact distances of the listed candidates (the query's lanes' columns in
                     // turn), kLoads at a time in flight

@@ -81,11 +81,10 @@ __global__ __launch_bounds__(256) void k_knn_grid(const KnnGrid* __restrict__ gp
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         bd[k] = r2max;
-        bi[k] = 0x7fffffff;
+        bi[k] = kKnnNone;
     }
     knn_walk<K>(g, c, p, self, bd, bi, sxyz, sidx, start, 0);
-#pragma unroll
-    for (int k = 0; k < K; ++k) nbr[(int64_t)self * K + k] = bi[k] == 0x7fffffff ? -1 : bi[k];
+    knn_store<K>(nbr, self, bi);
 }
 
 }  // namespace

@@ -482,7 +482,9 @@ epp_status epp_traj_thrust_rates_batch(const double* seg_times, const double* co
 epp_status epp_sample_uniform(uint64_t seed, const double lo[3], const double hi[3], int64_t n,
                               int64_t start, double* xyz, void* stream);
 /* k nearest neighbours (k in {4, 8, 16, 32}) of every node within max_dist (<= 0: no
- * limit), sorted by distance, ties to the lower index; missing entries are -1. */
+ * limit), sorted by distance, ties to the lower index; missing entries are -1.  The radius is
+ * exclusive on every path: node j is in range of node i iff the squared distance
+ * (dx^2 + dy^2) + dz^2, in double, is < max_dist^2; a neighbour at exactly max_dist is not. */
 epp_status epp_knn(const double* nodes, int32_t n, int32_t k, double max_dist, int32_t* nbr, void* stream);
 /* The two strategies behind epp_knn (same answers): all-pairs with LDS tiles, and a
  * uniform grid walked in shells. */

@@ -21,6 +21,7 @@ import oracle as O
 from eppamd import capi, config, synth
 
 from conftest import CONFIG, ROOT
+from knn_edge_inputs import knn_grid_shape
 from knn_ref import knn_ref as _knn_ref
 
 pytestmark = pytest.mark.gpu
@@ -107,14 +108,14 @@ def test_knn_tile_crowded_halo(k, tile, monkeypatch):
 def test_knn_tile_spilled_block(tile, monkeypatch):
     """One 4^3-cell block holds 129..160 nodes: k_knn_tile keeps two lanes per query for its
     first 128 and sends the rest to the retry list; the
-    table equals the all-pairs one.  The grid is replicated here (knn_grid_shape: ~1.5
+    table equals the all-pairs one.  The grid is restated (knn_edge_inputs.knn_grid_shape: ~1.5
     nodes per cell over the nodes' bounding box) to place the extra nodes in one block."""
     monkeypatch.setenv("EPP_KNN_TILE", tile)
     rs = np.random.RandomState(11)
     n0 = 20000
     nodes = rs.uniform(0.0, 8.0, (n0, 3))
     nodes[0], nodes[1] = [0.0, 0.0, 0.0], [8.0, 8.0, 8.0]  # the bounding box
-    h = np.cbrt(1.5 * 512.0 / (n0 + 64))
+    h = knn_grid_shape(nodes[0], nodes[1], n0 + 64)["h"]
     lo, hi = 4 * h, 8 * h  # block (1, 1, 1) of 4 cells per axis
     inside = lambda p: np.all((p >= lo) & (p < hi), axis=1)
     extra = 140 - int(inside(nodes).sum())
