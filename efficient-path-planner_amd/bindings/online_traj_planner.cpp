@@ -355,6 +355,38 @@ PYBIND11_MODULE(online_traj_planner, m) {
             py::arg("waypoint_sets"), py::arg("v_max"), py::arg("a_max"), py::arg("sampling_interval"),
             py::arg("g") = 9.81)
         .def(
+            "candidate_flyable_scales",  // fit + time scaling to thrust / rate / tilt limits of K waypoint sets (this build)
+            [](const epp::PathPlanner& self, const std::vector<py::object>& waypointSets, double vMax, double aMax,
+               const std::tuple<double, double, double, double, double>& limits) {
+                std::vector<std::vector<Vec3>> sets;
+                for (const auto& o : waypointSets) {
+                    Matrix w = to_matrix(o);
+                    if (w.cols != 3) throw std::invalid_argument("waypoints must be an (n, 3) array");
+                    std::vector<Vec3> wp;
+                    for (size_t i = 0; i < w.rows; ++i) wp.emplace_back(w(i, 0), w(i, 1), w(i, 2));
+                    sets.push_back(std::move(wp));
+                }
+                const epp::PathPlanner::FlightLimits lim{std::get<0>(limits), std::get<1>(limits), std::get<2>(limits),
+                                                         std::get<3>(limits), std::get<4>(limits)};
+                std::vector<double> scale, duration;
+                std::vector<int> status, violated;
+                {
+                    py::gil_scoped_release release;
+                    self.candidateFlyableScales(sets, vMax, aMax, lim, scale, duration, status, &violated);
+                }
+                const py::ssize_t K = (py::ssize_t)sets.size();
+                py::array_t<double> s(K), d(K);
+                py::array_t<int32_t> st(K), vi(K);
+                for (py::ssize_t i = 0; i < K; ++i) {
+                    s.mutable_data()[i] = scale[i];
+                    d.mutable_data()[i] = duration[i];
+                    st.mutable_data()[i] = status[i];
+                    vi.mutable_data()[i] = violated[i];
+                }
+                return py::make_tuple(s, d, st, vi);
+            },
+            py::arg("waypoint_sets"), py::arg("v_max"), py::arg("a_max"), py::arg("limits"))
+        .def(
             "first_hits",  // where every edge s1[i] -> s2[i] is first blocked, and by which OBB (this build)
             [](const epp::PathPlanner& self, const py::object& s1, const py::object& s2, bool canPassGate) {
                 Matrix a = to_matrix(s1), b = to_matrix(s2);

@@ -24,16 +24,33 @@ static void read3(py::object o, double* out) {
 static py::array_t<double> generate_trajectory(py::array_t<double, py::array::c_style | py::array::forcecast> waypoints,
                                                double v_max, double a_max, double sampling_intervall,
                                                double start_time_offset, py::object initial_vel,
-                                               py::object initial_acc, bool enforce_limits) {
+                                               py::object initial_acc, bool enforce_limits,
+                                               py::object thrust_limits) {
     if (waypoints.ndim() != 2 || waypoints.shape(1) != 3)
         throw std::invalid_argument("waypoints must be an (n, 3) array");
     double v0[3] = {0, 0, 0}, a0[3] = {0, 0, 0};
     read3(initial_vel, v0);
     read3(initial_acc, a0);
+    // thrustLimits = (g, f_min, f_max, rate_max, cos_tilt_min): the fit also time-scaled until
+    // its thrust, body rate and tilt are within them (epp_traj_scale_to_thrust_limits),
+    // independently of enforceLimits; None: the calls below, as before
+    double tl[5] = {0, 0, 0, 0, 0};
+    const bool flyable = !thrust_limits.is_none();
+    if (flyable) {
+        auto a = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(thrust_limits);
+        if (!a || a.size() != 5)
+            throw std::invalid_argument("thrustLimits must be (g, f_min, f_max, rate_max, cos_tilt_min)");
+        for (int i = 0; i < 5; ++i) tl[i] = a.data()[i];
+    }
     double* rows = nullptr;
     int64_t n = 0;
     epp_status rc;
-    {
+    if (flyable) {
+        py::gil_scoped_release release;
+        rc = epp_generate_trajectory_flyable_host(waypoints.data(), (int32_t)waypoints.shape(0), v_max, a_max,
+                                                  sampling_intervall, start_time_offset, v0, a0, enforce_limits ? 1 : 0,
+                                                  tl[0], tl[1], tl[2], tl[3], tl[4], &rows, &n, nullptr, nullptr);
+    } else {
         py::gil_scoped_release release;
         // enforceLimits: the fit time-scaled until its peak speed and acceleration are within
         // v_max / a_max (Trajectory::scaleSegmentTimesToMeetConstraints, src/trajectory.cpp:385-429)
@@ -104,7 +121,8 @@ PYBIND11_MODULE(polynomial_trajectory, m) {
     m.doc() = "MI355X min-snap trajectory generation (drop-in for poly_traj::generateTrajectory)";
     m.def("generate_trajectory", &generate_trajectory, py::arg("waypoints"), py::arg("v_max"), py::arg("a_max"),
           py::arg("sampling_intervall"), py::arg("startTimeOffset") = 0.0, py::arg("initialVel") = py::none(),
-          py::arg("initialAcc") = py::none(), py::arg("enforceLimits") = false);
+          py::arg("initialAcc") = py::none(), py::arg("enforceLimits") = false,
+          py::arg("thrustLimits") = py::none());
     m.def("max_velocity_and_acceleration", &max_velocity_and_acceleration, py::arg("waypoints"), py::arg("v_max"),
           py::arg("a_max"), py::arg("initialVel") = py::none(), py::arg("initialAcc") = py::none());
 }

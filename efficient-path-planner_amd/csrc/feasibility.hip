@@ -32,35 +32,18 @@
 
 #include "epp_internal.h"
 #include "launch_helpers.h"
+#include "poly_deriv.h"
 
 namespace epp {
 namespace {
 
-constexpr int N = 10;
+constexpr int N = kDerivCoeffs;  // (falling<K>, deriv<K>: poly_deriv.h)
 constexpr int kWave = 64;
 constexpr int kFeasWaves = 4;
 constexpr int kFeasBlock = kFeasWaves * kWave;
 constexpr int kMaxBisect = 52;
 constexpr int kMaxScaleRounds = 20;   // kMaxCounter, trajectory.cpp:388
 constexpr double kScaleTol = 1e-3;    // kTolerance, trajectory.cpp:389
-
-// j! / (j-K)!: the coefficient of t^(j-K) in the K-th derivative of t^j (Polynomial::
-// base_coefficients_, src/polynomial.cpp:145-160)
-template <int K>
-__device__ __forceinline__ constexpr double falling(int j) {
-    double f = 1.0;
-    for (int i = 0; i < K; ++i) f *= (double)(j - i);
-    return f;
-}
-
-// Polynomial::evaluate(t, K) (polynomial.h:136-149): Horner over the derivative's coefficients
-template <int K>
-__device__ __forceinline__ double deriv(const double (&c)[N], double t) {
-    double r = falling<K>(N - 1) * c[N - 1];
-#pragma unroll
-    for (int j = N - 2; j >= K; --j) r = r * t + falling<K>(j) * c[j];
-    return r;
-}
 
 struct Seg3 {
     double c[3][N];
@@ -274,15 +257,8 @@ __global__ __launch_bounds__(kFeasBlock) void k_traj_scale(double* seg_times, do
         const double s = fmax(1.0, fmax(vv, sqrt(av)));
         const double inv = 1.0 / s;
         for (int i = threadIdx.x; i < M; i += kFeasBlock) T[i] = T[i] * s;
-        for (int q = threadIdx.x; q < M * 3; q += kFeasBlock) {  // scalePolynomialInTime(1 / s)
-            double* c = C + (size_t)q * N;
-            double f = 1.0;
-#pragma unroll
-            for (int n = 0; n < N; ++n) {
-                c[n] = c[n] * f;
-                f = f * inv;
-            }
-        }
+        for (int q = threadIdx.x; q < M * 3; q += kFeasBlock)  // scalePolynomialInTime(1 / s)
+            scale_polynomial_in_time(C + (size_t)q * N, inv);
         product = product * s;
         __syncthreads();
     }

@@ -1302,9 +1302,12 @@ epp_status epp_generate_trajectory_times_host(const double* wp, int32_t n_wp, co
 // stream over pinned host buffers -- the batch fit (k_minsnap, one track), k_traj_scale,
 // then, after the host has run evaluateRange's sample recurrence on the SCALED times to
 // size the row buffer, k_sample_rows.
-epp_status epp_generate_trajectory_limited_host(const double* wp, int32_t n_wp, double v_max, double a_max, double dt,
-                                                double t0, const double v0[3], const double a0[3], double** rows_out,
-                                                int64_t* n_rows, double* scale_out) {
+// (enforce_va: k_traj_scale; tl != NULL: k_traj_thrust_scale under tl = [g, f_min, f_max,
+// rate_max, cos_tilt_min] after it -- epp_generate_trajectory_flyable_host; the limited call
+// is enforce_va with tl == NULL)
+static epp_status generate_scaled(const double* wp, int32_t n_wp, double v_max, double a_max, double dt, double t0,
+                                  const double v0[3], const double a0[3], bool enforce_va, const double* tl,
+                                  double** rows_out, int64_t* n_rows, double* scale_out, double* scale_thrust) {
     if (!rows_out || !n_rows || (n_wp > 0 && !wp)) {
         set_error("generateTrajectory: invalid argument");
         return EPP_ERR_INVALID_ARGUMENT;
@@ -1315,9 +1318,14 @@ epp_status epp_generate_trajectory_limited_host(const double* wp, int32_t n_wp, 
         set_error("At least two waypoints are required");  // trajectory_generator.cpp:24
         return EPP_ERR_INVALID_ARGUMENT;
     }
-    if (!(v_max > 0.0) || !(a_max > 0.0)) {
+    if (enforce_va && (!(v_max > 0.0) || !(a_max > 0.0))) {
         set_error("generateTrajectory: v_max and a_max must be greater than zero to enforce them");
         return EPP_ERR_INVALID_ARGUMENT;
+    }
+    if (tl) {  // the limits' conditions, before any device work (an empty batch launches nothing)
+        const epp_status bad = epp_traj_scale_to_thrust_limits(nullptr, nullptr, nullptr, 0, tl[0], tl[1], tl[2], tl[3],
+                                                               tl[4], nullptr, nullptr, nullptr, nullptr);
+        if (bad) return bad;
     }
     const int M = n_wp - 1;
     for (int i = 0; i < M; ++i)
@@ -1331,8 +1339,8 @@ epp_status epp_generate_trajectory_limited_host(const double* wp, int32_t n_wp, 
         return EPP_ERR_HIP;
     }
     epp_status rc;
-    const size_t nd = (size_t)3 * n_wp + 6 + (size_t)M * 31 + 2;  // doubles before the int32 words
-    hipError_t e = c.ensure(nd * 8 + 16, 0, 0);
+    const size_t nd = (size_t)3 * n_wp + 6 + (size_t)M * 31 + 3;  // doubles before the int32 words
+    hipError_t e = c.ensure(nd * 8 + 24, 0, 0);
     if (e != hipSuccess) return buffers_error(e);
     double* h_wp = c.h_in.as<double>();
     double* h_v0 = h_wp + 3 * n_wp;
@@ -1340,33 +1348,41 @@ epp_status epp_generate_trajectory_limited_host(const double* wp, int32_t n_wp, 
     double* h_T = h_a0 + 3;
     double* h_C = h_T + M;
     double* h_scale = h_C + (size_t)M * 30;
-    double* h_t0 = h_scale + 1;
+    double* h_t0 = h_scale + 2;  // (h_scale: [v / a, thrust])
     int32_t* h_off = reinterpret_cast<int32_t*>(h_t0 + 1);
-    int32_t* h_st = h_off + 2;  // [fit, scale]
+    int32_t* h_st = h_off + 2;  // [fit, scale, thrust scale]
     std::memcpy(h_wp, wp, (size_t)n_wp * 24);
     for (int k = 0; k < 3; ++k) {
         h_v0[k] = v0 ? v0[k] : 0.0;
         h_a0[k] = a0 ? a0[k] : 0.0;
     }
-    *h_scale = 1.0;
+    h_scale[0] = h_scale[1] = 1.0;
     *h_t0 = t0;
     h_off[0] = 0;
     h_off[1] = n_wp;
-    h_st[0] = h_st[1] = -100;
+    h_st[0] = -100;
+    h_st[1] = enforce_va ? -100 : 0;
+    h_st[2] = tl ? -100 : 0;
     if ((rc = minsnap_batch(h_wp, h_off, 1, v_max, a_max, h_v0, h_a0, nullptr, h_T, h_C, h_st, c.s,
                             "generateTrajectory", M)))
         return rc;
-    if ((rc = epp_traj_scale_to_limits(h_T, h_C, h_off, 1, v_max, a_max, h_scale, h_st + 1, c.s))) return rc;
+    if (enforce_va && (rc = epp_traj_scale_to_limits(h_T, h_C, h_off, 1, v_max, a_max, h_scale, h_st + 1, c.s)))
+        return rc;
+    if (tl && (rc = epp_traj_scale_to_thrust_limits(h_T, h_C, h_off, 1, tl[0], tl[1], tl[2], tl[3], tl[4], h_scale + 1,
+                                                    h_st + 2, nullptr, c.s)))
+        return rc;
     e = hipStreamSynchronize(c.s);
     if (e != hipSuccess) {
         set_error(std::string("generateTrajectory: ") + hipGetErrorString(e));
         return EPP_ERR_HIP;
     }
-    if (h_st[0] != 0 || h_st[1] != 0) {
+    if (h_st[0] != 0 || h_st[1] != 0 || h_st[2] != 0) {
         set_error(h_st[0] == -2   ? "Segment times need to be greater than zero"
                   : h_st[0] != 0  ? "min-snap solve failed"
                   : h_st[1] == 1  ? "generateTrajectory: v_max / a_max not met after 20 rounds of time scaling"
-                                  : "generateTrajectory: the fit is not finite");
+                  : h_st[1] == 0 && h_st[2] == 1
+                      ? "generateTrajectory: the thrust limits are not met at 1024 times the duration"
+                      : "generateTrajectory: the fit is not finite");
         return EPP_ERR_RUNTIME;
     }
     int64_t R = 0;
@@ -1399,10 +1415,30 @@ epp_status epp_generate_trajectory_limited_host(const double* wp, int32_t n_wp, 
         }
         std::memcpy(rows, c.h_out.p, (size_t)R * 80);
     }
-    if (scale_out) *scale_out = *h_scale;
+    if (scale_out) *scale_out = h_scale[0];
+    if (scale_thrust) *scale_thrust = h_scale[1];
     *rows_out = rows;
     *n_rows = R;
     return EPP_OK;
+}
+
+epp_status epp_generate_trajectory_limited_host(const double* wp, int32_t n_wp, double v_max, double a_max, double dt,
+                                                double t0, const double v0[3], const double a0[3], double** rows_out,
+                                                int64_t* n_rows, double* scale_out) {
+    return generate_scaled(wp, n_wp, v_max, a_max, dt, t0, v0, a0, true, nullptr, rows_out, n_rows, scale_out,
+                           nullptr);
+}
+
+// The same with epp_traj_scale_to_thrust_limits (thrust_scale.hip) after the v / a scaling,
+// which enforce_va switches: one launch more on the same stream, before the one synchronisation.
+epp_status epp_generate_trajectory_flyable_host(const double* wp, int32_t n_wp, double v_max, double a_max, double dt,
+                                                double t0, const double v0[3], const double a0[3], int32_t enforce_va,
+                                                double g, double f_min, double f_max, double rate_max,
+                                                double cos_tilt_min, double** rows_out, int64_t* n_rows,
+                                                double* scale_va, double* scale_thrust) {
+    const double tl[5] = {g, f_min, f_max, rate_max, cos_tilt_min};
+    return generate_scaled(wp, n_wp, v_max, a_max, dt, t0, v0, a0, enforce_va != 0, tl, rows_out, n_rows, scale_va,
+                           scale_thrust);
 }
 
 #ifdef EPP_REFIT_TL

@@ -107,6 +107,11 @@ def lib() -> C.CDLL:
             "epp_sample_derivative_batch": (i32, [vp, vp, vp, i32, dp, i32, vp, vp, vp]),
             "epp_thrust_rates": (i32, [vp, vp, i64, dp, vp, vp, vp, vp]),
             "epp_traj_thrust_rates_batch": (i32, [vp, vp, vp, i32, dp, dp, vp, vp, vp]),
+            "epp_traj_thrust_grid_batch": (i32, [vp, vp, vp, i32, vp, dp, vp, vp]),
+            "epp_traj_scale_to_thrust_limits": (i32, [vp, vp, vp, i32, dp, dp, dp, dp, dp, vp, vp, vp, vp]),
+            "epp_generate_trajectory_flyable_host": (i32, [vp, i32, dp, dp, dp, dp, vp, vp, i32, dp, dp, dp, dp, dp,
+                                                           C.POINTER(C.POINTER(C.c_double)), C.POINTER(i64),
+                                                           C.POINTER(C.c_double), C.POINTER(C.c_double)]),
             "epp_generate_trajectory_limited_host": (i32, [vp, i32, dp, dp, dp, dp, vp, vp,
                                                            C.POINTER(C.POINTER(C.c_double)), C.POINTER(i64),
                                                            C.POINTER(C.c_double)]),
@@ -173,6 +178,7 @@ EXPORTED = [
     "epp_traj_check_batch", "epp_traj_sweep_batch", "epp_states_clearance", "epp_traj_clearance_batch",
     "epp_motions_first_hit", "epp_traj_first_hit_batch", "epp_gates_crossed", "epp_traj_gate_pass_batch",
     "epp_sample_derivative_batch", "epp_thrust_rates", "epp_traj_thrust_rates_batch", "epp_device_cu_count",
+    "epp_traj_thrust_grid_batch", "epp_traj_scale_to_thrust_limits", "epp_generate_trajectory_flyable_host",
 ]
 
 
@@ -746,6 +752,65 @@ def generate_trajectory_limited(waypoints, v_max, a_max, dt, t0=0.0, v0=(0, 0, 0
     out = np.ctypeslib.as_array(rows, shape=(n.value * 10,)).copy().reshape(-1, 10) if n.value else np.zeros((0, 10))
     lib().epp_host_free(C.cast(rows, C.c_void_p))
     return (out, scale.value) if return_scale else out
+
+
+def thrust_grid(Ts, Cs, g: float = GRAVITY, scale=None):
+    """epp_traj_thrust_grid_batch on the lists minsnap_batch returns: per track [f_min, t_fmin,
+    f_max, t_fmax, rate_max, t_rate, cos_min, t_cos] over the 65 grid points of every segment
+    at the per-track scale (None: 1), times in the input track's time.  Returns float64[n, 8]."""
+    nt = len(Ts)
+    d_T, d_C, d_off, _, _ = _upload_tracks(Ts, Cs)
+    d_out = DeviceBuffer(64 * max(nt, 1))
+    d_s = None
+    if scale is not None:
+        sc = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, np.float64), (nt,)))
+        d_s = DeviceBuffer.from_array(sc if nt else np.zeros(1))
+    check(lib().epp_traj_thrust_grid_batch(d_T.ptr, d_C.ptr, d_off.ptr, nt, d_s.ptr if d_s else None, float(g),
+                                           d_out.ptr, None))
+    sync()
+    return d_out.download(np.float64, 8 * nt).reshape(nt, 8)
+
+
+def scale_to_thrust_limits(Ts, Cs, g, f_min, f_max, rate_max, cos_tilt_min):
+    """epp_traj_scale_to_thrust_limits: (new seg_times list, new coeffs list, scale array,
+    status array, violated array)."""
+    nt = len(Ts)
+    d_T, d_C, d_off, off, nseg = _upload_tracks(Ts, Cs)
+    d_sc, d_st, d_vi = DeviceBuffer(8 * max(nt, 1)), DeviceBuffer(4 * max(nt, 1)), DeviceBuffer(4 * max(nt, 1))
+    check(lib().epp_traj_scale_to_thrust_limits(d_T.ptr, d_C.ptr, d_off.ptr, nt, float(g), float(f_min),
+                                                float(f_max), float(rate_max), float(cos_tilt_min), d_sc.ptr,
+                                                d_st.ptr, d_vi.ptr, None))
+    sync()
+    T = d_T.download(np.float64, nseg)
+    Cf = d_C.download(np.float64, nseg * 30).reshape(nseg, 3, 10)
+    Tn, Cn = [], []
+    for k in range(nt):
+        a, b = int(off[k]) - k, int(off[k + 1]) - k - 1
+        Tn.append(T[a:max(a, b)])
+        Cn.append(Cf[a:max(a, b)])
+    return Tn, Cn, d_sc.download(np.float64, nt), d_st.download(np.int32, nt), d_vi.download(np.int32, nt)
+
+
+def generate_trajectory_flyable(waypoints, v_max, a_max, dt, limits, t0=0.0, v0=(0, 0, 0), a0=(0, 0, 0),
+                                enforce_va=False, return_scales=False):
+    """epp_generate_trajectory_flyable_host: generate_trajectory with the fit time-scaled to
+    meet v_max / a_max when enforce_va, then the thrust, body-rate and tilt limits
+    limits = (g, f_min, f_max, rate_max, cos_tilt_min).  return_scales: (rows, scale_va,
+    scale_thrust)."""
+    wp = np.ascontiguousarray(np.asarray(waypoints, np.float64).reshape(-1, 3))
+    v0 = np.ascontiguousarray(v0, np.float64)
+    a0 = np.ascontiguousarray(a0, np.float64)
+    g, f_min, f_max, rate_max, cos_tilt_min = (float(x) for x in limits)
+    rows = C.POINTER(C.c_double)()
+    n = C.c_int64(0)
+    s_va, s_th = C.c_double(1.0), C.c_double(1.0)
+    check(lib().epp_generate_trajectory_flyable_host(_ptr(wp), len(wp), float(v_max), float(a_max), float(dt),
+                                                     float(t0), _ptr(v0), _ptr(a0), 1 if enforce_va else 0, g, f_min,
+                                                     f_max, rate_max, cos_tilt_min, C.byref(rows), C.byref(n),
+                                                     C.byref(s_va), C.byref(s_th)))
+    out = np.ctypeslib.as_array(rows, shape=(n.value * 10,)).copy().reshape(-1, 10) if n.value else np.zeros((0, 10))
+    lib().epp_host_free(C.cast(rows, C.c_void_p))
+    return (out, s_va.value, s_th.value) if return_scales else out
 
 
 def check_and_generate_trajectory(world: "World", check_xyz, min_distance, waypoints, v_max, a_max, dt, t0=0.0,

@@ -51,6 +51,10 @@
  *   epp_thrust_rates / epp_traj_thrust_rates_batch
  *       no reference counterpart: the thrust, the roll / pitch body rate and the tilt a
  *       quadrotor needs at a sample, and their extremes over every fitted track's rows.
+ *   epp_traj_thrust_grid_batch / epp_traj_scale_to_thrust_limits
+ *       Trajectory::scaleSegmentTimesToMeetConstraints (external/poly_traj/src/trajectory.cpp:
+ *       385-429) extended from |v| and |a| to thrust, body-rate and tilt limits: the extremes
+ *       over the peak search's grid points at a scale, and the search for the scale.
  */
 #ifndef EPP_H_
 #define EPP_H_
@@ -475,6 +479,61 @@ epp_status epp_traj_thrust_rates_batch(const double* seg_times, const double* co
                                        int32_t n_tracks, double dt, double g, double* out, int64_t* rows,
                                        void* stream);
 
+/* ---- time scaling to thrust, body-rate and tilt limits (device pointers).  The reference
+ * stretches a track that violates v_max / a_max (Trajectory::scaleSegmentTimesToMeetConstraints,
+ * external/poly_traj/src/trajectory.cpp:385-429; epp_traj_scale_to_limits above); these two
+ * calls extend that behaviour to the quantities of epp_thrust_rates.  Under x(t / s) the
+ * thrust is |a / s^2 + g e_z|, no power of s, so the scale is searched for, not computed.
+ * One definition (csrc/thrust_scale.h), every operation one IEEE fp64 operation:
+ *   grid points: segment m of time T_m gives tau_i = T_m * (i / 64), i = 0..63, and tau = T_m
+ *       (the 65 points epp_traj_peaks looks at); a = p''(tau), j = p'''(tau) of the input track
+ *       by Horner over the derivative's coefficients; a point's time is the sum of the earlier
+ *       segment times plus tau;
+ *   at scale s: s2 = s * s, s3 = s2 * s, a_s = a / s2, j_s = j / s3 (divisions), then the
+ *       arithmetic of epp_thrust_rates on (a_s, j_s, g).
+ * Like epp_traj_peaks they look at 65 points per segment: a bump narrower than T / 64 can be
+ * missed, and the rows every dt of the scaled track are other points than the grid (a caller
+ * who needs the rows' answer runs epp_traj_thrust_rates_batch on the result).  Both are
+ * stream-ordered, with no host synchronisation and no allocation, so they can be captured. */
+/* The four extremes over the grid points of every track at the scale scale_in[k] (device
+ * f64; NULL: 1), in epp_traj_thrust_rates_batch's layout:
+ *   out[k * 8 + ..] (device f64) = [f_min, t_fmin, f_max, t_fmax, rate_max, t_rate, cos_min, t_cos]
+ * The times are in the INPUT track's time (not multiplied by the scale).  A value replaces the
+ * running extreme only on strict < or >, ties go to the earliest time, a NaN never wins; a
+ * track that is invalid as for epp_traj_peaks (one waypoint, a segment time <= 0, non-finite
+ * input) and a quantity that is NaN on every point keep the identities [+inf, -1, -inf, -1,
+ * -inf, -1, +inf, -1].  A scale that is not finite and > 0 gives what the operations give.
+ * EPP_ERR_INVALID_ARGUMENT (before any device work) for n_tracks < 0, a non-finite g, or a
+ * NULL seg_times, coeffs, wp_offsets or out with n_tracks > 0; n_tracks == 0 launches nothing. */
+epp_status epp_traj_thrust_grid_batch(const double* seg_times, const double* coeffs, const int32_t* wp_offsets,
+                                      int32_t n_tracks, const double* scale_in, double g, double* out, void* stream);
+/* Scales every track of the batch in time, in place, until no grid point violates
+ *   thrust < f_min (bit 0) | thrust > f_max (bit 1) | rate > rate_max (bit 2) | cos_tilt < cos_tilt_min (bit 3)
+ * (a NaN violates nothing), the whole search and the apply in one launch.  A track feasible at
+ * scale 1 comes back bit for bit, scale 1.0, status 0.  Otherwise hi = 2 is doubled while the
+ * track is infeasible at hi, up to 1024 (infeasible there: status 1, scale 1.0, the track
+ * untouched); then lo = hi / 2 and exactly 12 rounds of mid = 0.5 * (lo + hi), hi = mid when
+ * feasible at mid, else lo = mid.  scale[k] = hi is applied as one round of
+ * epp_traj_scale_to_limits: T[i] = T[i] * s and every polynomial through
+ * scalePolynomialInTime(1 / s).  status[k] (device int32): 0, 1, or -1 for an invalid track
+ * (as epp_traj_peaks; untouched, scale 1.0).  violated[k] (device int32, may be NULL): the bits
+ * violated at scale 1; 0 for a feasible or invalid track.
+ * The limits must satisfy 0 <= f_min < g < f_max, rate_max > 0, cos_tilt_min < 1, g finite and
+ * > 0: then every finite track is feasible for a large enough scale (thrust -> g, rate -> 0,
+ * cos_tilt -> 1).  f_max = +inf, rate_max = +inf and cos_tilt_min <= -1 switch a limit off,
+ * f_min = 0 the lower thrust bound.  Only f_max is monotone in the scale; f_min, the rate and
+ * the tilt are not (a track can be feasible at a small scale with its thrust axis pointing
+ * down), so the answer is A feasible scale >= 1 with an infeasible one within 2^-12 below it
+ * (or exactly 1), not a proven minimum, and a track feasible at 1 is taken as it is.  Scaling
+ * alters a non-zero start velocity, as epp_traj_scale_to_limits does.
+ * EPP_ERR_INVALID_ARGUMENT (before any device work) for limits outside those conditions, a
+ * non-finite g, n_tracks < 0, or a NULL seg_times, coeffs, wp_offsets, scale or status with
+ * n_tracks > 0; n_tracks == 0 launches nothing. */
+epp_status epp_traj_scale_to_thrust_limits(double* seg_times, double* coeffs, const int32_t* wp_offsets,
+                                           int32_t n_tracks, double g, double f_min, double f_max, double rate_max,
+                                           double cos_tilt_min, double* scale, int32_t* status, int32_t* violated,
+                                           void* stream);
+
 /* ---- batch planner building blocks (device pointers) ------------------------------- */
 /* Replace OMPL's sampler / nearest-neighbour structure behind PathPlanner::planPath
  * (src/PathPlanner.cpp:80-158).  Counter-based uniform states in [lo, hi]:
@@ -614,6 +673,20 @@ epp_status epp_generate_trajectory_times_host(const double* wp, int32_t n_wp, co
 epp_status epp_generate_trajectory_limited_host(const double* wp, int32_t n_wp, double v_max, double a_max,
                                                 double dt, double t0, const double v0[3], const double a0[3],
                                                 double** rows, int64_t* n_rows, double* scale_out);
+/* epp_generate_trajectory_host made flyable: the fit, then epp_traj_scale_to_limits when
+ * enforce_va != 0, then epp_traj_scale_to_thrust_limits under (g, f_min, f_max, rate_max,
+ * cos_tilt_min), then the sampling of the scaled trajectory.  Scaling up keeps |v| and |a|
+ * within their limits, so that order is safe.  Launches over pinned host buffers as
+ * epp_generate_trajectory_limited_host; the rows are those of epp_sample_batch on the two
+ * calls' output.  *scale_va, *scale_thrust (may be NULL): the two factors applied (1.0: none).
+ * Errors as epp_generate_trajectory_limited_host (v_max, a_max > 0 are asked for only when
+ * enforce_va); also EPP_ERR_INVALID_ARGUMENT for limits epp_traj_scale_to_thrust_limits
+ * rejects, EPP_ERR_RUNTIME when the track is still infeasible at scale 1024. */
+epp_status epp_generate_trajectory_flyable_host(const double* wp, int32_t n_wp, double v_max, double a_max,
+                                                double dt, double t0, const double v0[3], const double a0[3],
+                                                int32_t enforce_va, double g, double f_min, double f_max,
+                                                double rate_max, double cos_tilt_min, double** rows,
+                                                int64_t* n_rows, double* scale_va, double* scale_thrust);
 /* The C5 online step's two GPU calls in ONE launch (an addition of this build; the
  * reference makes them one after the other: PathPlanner::checkTrajectoryValidity,
  * src/PathPlanner.cpp:267-280, then poly_traj::generateTrajectory, src/

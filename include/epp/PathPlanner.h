@@ -187,6 +187,23 @@ public:
     // checkCandidateTrajectories.
     void candidateThrustRates(const std::vector<std::vector<Vec3>>& waypointSets, double v_max, double a_max, double dt,
                               double g, std::vector<double>& out, std::vector<long>* rows = nullptr) const;
+    // The duration at which each of K candidate waypoint sets' trajectories becomes flyable (an
+    // addition of this build), to rank candidates: the fit of every set as above and, on the
+    // same stream with one synchronisation, epp_traj_scale_to_thrust_limits (include/epp.h)
+    // under `limits`.  scale[k]: the factor applied to set k's segment times (1.0: flyable as
+    // fitted); duration[k]: the sum of the scaled segment times; status[k]: 0, or 1 when the
+    // set is still infeasible at scale 1024 (duration then that of the fit); violated
+    // (optional): the limits violated as fitted, bit 0 f_min, bit 1 f_max, bit 2 rate, bit 3
+    // tilt.  The search looks at 65 points per segment, and only f_max is monotone in the
+    // scale: the answer is a feasible scale, not a proven minimum.  Throws as
+    // candidateThrustRates, and std::invalid_argument for limits outside 0 <= fMin < g < fMax,
+    // rateMax > 0, cosTiltMin < 1.
+    struct FlightLimits {
+        double g, fMin, fMax, rateMax, cosTiltMin;
+    };
+    void candidateFlyableScales(const std::vector<std::vector<Vec3>>& waypointSets, double v_max, double a_max,
+                                const FlightLimits& limits, std::vector<double>& scale, std::vector<double>& duration,
+                                std::vector<int>& status, std::vector<int>* violated = nullptr) const;
     std::vector<Vec3> includeGates2(std::vector<std::vector<Vec3>> waypoints) const;
     // planPaths of consecutive gate-to-gate segments, then includeGates2 of their paths (an
     // addition of this build, for OnlineTrajGenerator::preComputeTraj): the same answers as
