@@ -1,6 +1,6 @@
 // collision_common.h — device helpers shared by the OBB kernels (the states_*.hip and
 // motions_*.hip kernel files, small.hip, clearance.hip, first_hit.hip, trajcheck.hip,
-// minsnap.hip) and the allow_lds launch helper; the other host-side launch helpers are in
+// minsnap_refit.hip) and the allow_lds launch helper; the other host-side launch helpers are in
 // launch_helpers.h.  What only the state kernels use is in states_kernels.h and states_*.hip.
 //
 // All decision arithmetic is IEEE fp64 with contraction disabled (-ffp-contract=off), in

@@ -1,5 +1,5 @@
 // completion.h — the completion slots of the synchronous latency paths, both halves (the
-// small state / ray checks of small.hip, the refit kernels of minsnap.hip, k_pb_emit of
+// small state / ray checks of small.hip, the refit kernels of minsnap_refit.hip, k_pb_emit of
 // plan_batch.hip and their hosts).  A kernel's workgroups write their results into pinned host
 // memory and then each publishes the call's sequence number in its own pinned slot
 // (publish_done); the host polls the slots (wait_done) instead of synchronising the stream.
@@ -20,7 +20,7 @@ namespace epp {
 // every wave waits until its own stores are acknowledged by the memory system
 // (s_waitcnt vmcnt(0) lgkmcnt(0)), and the barrier orders them before that store, whose
 // release (an L2 write-back of the XCD, then the store) covers them.  The wait is inline
-// assembly with a "memory" clobber (as wave_sync_lds, minsnap.hip): the compiler
+// assembly with a "memory" clobber (as wave_sync_lds, minsnap_solve.h): the compiler
 // takes the s_waitcnt builtin to touch no memory and may move stores across it; the clobber
 // keeps every earlier store before the wait.  One system-scope release per workgroup
 // instead of a __threadfence_system() per wave: k_motions_small at 1,024 edges (64

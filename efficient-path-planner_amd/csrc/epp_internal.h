@@ -47,7 +47,7 @@
 #include "epp.h"
 
 namespace epp {
-// poly_traj::generateTrajectory of one track on the device (k_refit, minsnap.hip); the R
+// poly_traj::generateTrajectory of one track on the device (k_refit, minsnap_refit.hip); the R
 // sampled rows (R x 10 doubles) are copied into the buffer alloc(ctx, R) returns (NULL:
 // out of memory).  times: the caller's segment times, or NULL for Nfabian's.
 epp_status generate_trajectory_into(const double* wp, int32_t n_wp, const double* times, double v_max,

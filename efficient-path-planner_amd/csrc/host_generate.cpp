@@ -1,0 +1,220 @@
+// host_generate.cpp — the C entry points of the single-track host calls: generateTrajectory
+// (and its variants with caller times and with the fused check) over the refit
+// (minsnap_refit.hip), and the fits scaled to limits before the sampling (generate_scaled).
+// Host code only: the kernels are enqueued through minsnap_kernels.h and the C ABI.
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+
+#include "epp.h"
+#include "epp_internal.h"
+#include "minsnap_kernels.h"
+#include "stream_bufs.h"
+#include "traj_sample.h"
+
+namespace epp {
+namespace {
+
+double* malloc_rows(void* ctx, int64_t R) {
+    double* p = (double*)std::malloc((size_t)std::max<int64_t>(R, 1) * 80);
+    *static_cast<double**>(ctx) = p;
+    return p;
+}
+// a failed call hands out no rows: frees what malloc_rows allocated
+epp_status free_rows_on_failure(epp_status rc, double** rows_out) {
+    if (rc != EPP_OK && *rows_out) {
+        std::free(*rows_out);
+        *rows_out = nullptr;
+    }
+    return rc;
+}
+epp_status generate_trajectory(const double* wp, int32_t n_wp, const double* times, double v_max, double a_max,
+                               double dt, double t0, const double v0[3], const double a0[3], double** rows_out,
+                               int64_t* n_rows) {
+    if (!rows_out || !n_rows) {
+        set_error("generateTrajectory: invalid argument");
+        return EPP_ERR_INVALID_ARGUMENT;
+    }
+    *rows_out = nullptr;
+    return free_rows_on_failure(
+        generate_trajectory_into(wp, n_wp, times, v_max, a_max, dt, t0, v0, a0, malloc_rows, rows_out, n_rows),
+        rows_out);
+}
+
+// generateTrajectory followed by Trajectory::scaleSegmentTimesToMeetConstraints
+// (src/trajectory.cpp:385-429) before the sampling: three launches on the calling thread's
+// stream over pinned host buffers (StreamBufs: h_in the track's inputs, times, coefficients
+// and flags, h_out the rows; the kernels read and write them directly) -- the batch fit
+// (k_minsnap, one track), k_traj_scale, then, after the host has run evaluateRange's sample
+// recurrence on the SCALED times to size the row buffer, the row sampler.
+// (enforce_va: k_traj_scale; tl != NULL: k_traj_thrust_scale under tl = [g, f_min, f_max,
+// rate_max, cos_tilt_min] after it -- epp_generate_trajectory_flyable_host; the limited call
+// is enforce_va with tl == NULL)
+epp_status generate_scaled(const double* wp, int32_t n_wp, double v_max, double a_max, double dt, double t0,
+                           const double v0[3], const double a0[3], bool enforce_va, const double* tl,
+                           double** rows_out, int64_t* n_rows, double* scale_out, double* scale_thrust) {
+    if (!rows_out || !n_rows || (n_wp > 0 && !wp)) {
+        set_error("generateTrajectory: invalid argument");
+        return EPP_ERR_INVALID_ARGUMENT;
+    }
+    *rows_out = nullptr;
+    *n_rows = 0;
+    if (n_wp < 2) {
+        set_error("At least two waypoints are required");  // trajectory_generator.cpp:24
+        return EPP_ERR_INVALID_ARGUMENT;
+    }
+    if (enforce_va && (!(v_max > 0.0) || !(a_max > 0.0))) {
+        set_error("generateTrajectory: v_max and a_max must be greater than zero to enforce them");
+        return EPP_ERR_INVALID_ARGUMENT;
+    }
+    if (tl) {  // the limits' conditions, before any device work (an empty batch launches nothing)
+        const epp_status bad = epp_traj_scale_to_thrust_limits(nullptr, nullptr, nullptr, 0, tl[0], tl[1], tl[2], tl[3],
+                                                               tl[4], nullptr, nullptr, nullptr, nullptr);
+        if (bad) return bad;
+    }
+    const int M = n_wp - 1;
+    for (int i = 0; i < M; ++i)
+        if (!(nfabian(wp + 3 * i, wp + 3 * (i + 1), v_max, a_max) > 0)) {  // CHECK_GT(segment_time, 0)  impl :297
+            set_error(fit_status_message(-2));
+            return EPP_ERR_RUNTIME;
+        }
+    static thread_local StreamBufs c;
+    if (c.bind() != hipSuccess) {
+        set_error("generateTrajectory: stream");
+        return EPP_ERR_HIP;
+    }
+    epp_status rc;
+    const size_t nd = (size_t)3 * n_wp + 6 + (size_t)M * 31 + 3;  // doubles before the int32 words
+    hipError_t e = c.ensure(nd * 8 + 24, 0, 0);
+    if (e != hipSuccess) return buffers_error(e);
+    double* h_wp = c.h_in.as<double>();
+    double* h_v0 = h_wp + 3 * n_wp;
+    double* h_a0 = h_v0 + 3;
+    double* h_T = h_a0 + 3;
+    double* h_C = h_T + M;
+    double* h_scale = h_C + (size_t)M * 30;
+    double* h_t0 = h_scale + 2;  // (h_scale: [v / a, thrust])
+    int32_t* h_off = reinterpret_cast<int32_t*>(h_t0 + 1);
+    int32_t* h_st = h_off + 2;  // [fit, scale, thrust scale]
+    std::memcpy(h_wp, wp, (size_t)n_wp * 24);
+    for (int k = 0; k < 3; ++k) {
+        h_v0[k] = v0 ? v0[k] : 0.0;
+        h_a0[k] = a0 ? a0[k] : 0.0;
+    }
+    h_scale[0] = h_scale[1] = 1.0;
+    *h_t0 = t0;
+    h_off[0] = 0;
+    h_off[1] = n_wp;
+    h_st[0] = -100;
+    h_st[1] = enforce_va ? -100 : 0;
+    h_st[2] = tl ? -100 : 0;
+    if ((rc = launch_minsnap_track(h_wp, h_off, M, v_max, a_max, h_v0, h_a0, h_T, h_C, h_st, c.s, "generateTrajectory")))
+        return rc;
+    if (enforce_va && (rc = epp_traj_scale_to_limits(h_T, h_C, h_off, 1, v_max, a_max, h_scale, h_st + 1, c.s)))
+        return rc;
+    if (tl && (rc = epp_traj_scale_to_thrust_limits(h_T, h_C, h_off, 1, tl[0], tl[1], tl[2], tl[3], tl[4], h_scale + 1,
+                                                    h_st + 2, nullptr, c.s)))
+        return rc;
+    e = hipStreamSynchronize(c.s);
+    if (e != hipSuccess) {
+        set_error(std::string("generateTrajectory: ") + hipGetErrorString(e));
+        return EPP_ERR_HIP;
+    }
+    if (h_st[0] != 0 || h_st[1] != 0 || h_st[2] != 0) {
+        set_error(fit_status_message(h_st[0], h_st[1], h_st[2]));
+        return EPP_ERR_RUNTIME;
+    }
+    int64_t R = 0;
+    if (dt > 0) {  // Trajectory::evaluateRange's recurrence on the scaled times (exact count)
+        RangeIter it;
+        it.init(h_T, M);
+        R = range_count(it, dt);
+    }
+    double* rows = (double*)std::malloc((size_t)std::max<int64_t>(R, 1) * 80);
+    if (!rows) {
+        set_error("generateTrajectory: out of host memory");
+        return EPP_ERR_RUNTIME;
+    }
+    if (R) {
+        rc = EPP_OK;
+        if ((e = c.ensure(0, (size_t)R * 80, 0)) != hipSuccess) rc = buffers_error(e);
+        if (!rc)
+            rc = launch_sample_rows_track(h_T, h_C, h_off, M, dt, h_t0, c.h_out.as<double>(), R, c.s,
+                                          "generateTrajectory");
+        if (!rc && (e = hipStreamSynchronize(c.s)) != hipSuccess) {
+            set_error(std::string("generateTrajectory: ") + hipGetErrorString(e));
+            rc = EPP_ERR_HIP;
+        }
+        if (rc) {
+            std::free(rows);
+            return rc;
+        }
+        std::memcpy(rows, c.h_out.p, (size_t)R * 80);
+    }
+    if (scale_out) *scale_out = h_scale[0];
+    if (scale_thrust) *scale_thrust = h_scale[1];
+    *rows_out = rows;
+    *n_rows = R;
+    return EPP_OK;
+}
+
+}  // namespace
+}  // namespace epp
+
+using namespace epp;
+
+extern "C" {
+
+epp_status epp_generate_trajectory_host(const double* wp, int32_t n_wp, double v_max, double a_max, double dt,
+                                        double t0, const double v0[3], const double a0[3], double** rows_out,
+                                        int64_t* n_rows) {
+    return generate_trajectory(wp, n_wp, nullptr, v_max, a_max, dt, t0, v0, a0, rows_out, n_rows);
+}
+
+epp_status epp_check_and_generate_trajectory_host(const epp_world* world, const double* check_xyz, int64_t n_check,
+                                                  double min_distance, uint8_t* check_valid, const double* wp,
+                                                  int32_t n_wp, double v_max, double a_max, double dt, double t0,
+                                                  const double v0[3], const double a0[3], double** rows_out,
+                                                  int64_t* n_rows) {
+    if (!rows_out || !n_rows || !world || n_check < 0 || (n_check > 0 && (!check_xyz || !check_valid))) {
+        set_error("epp_check_and_generate_trajectory_host: invalid argument");
+        return EPP_ERR_INVALID_ARGUMENT;
+    }
+    *rows_out = nullptr;
+    const FusedCheck chk{world, check_xyz, n_check, min_distance, check_valid};
+    return free_rows_on_failure(
+        check_and_generate_into(&chk, wp, n_wp, nullptr, v_max, a_max, dt, t0, v0, a0, malloc_rows, rows_out, n_rows),
+        rows_out);
+}
+
+epp_status epp_generate_trajectory_times_host(const double* wp, int32_t n_wp, const double* seg_times, double dt,
+                                              double t0, const double v0[3], const double a0[3], double** rows_out,
+                                              int64_t* n_rows) {
+    if (n_wp >= 2 && !seg_times) {
+        set_error("generateTrajectory: invalid argument");
+        return EPP_ERR_INVALID_ARGUMENT;
+    }
+    return generate_trajectory(wp, n_wp, seg_times, 0.0, 0.0, dt, t0, v0, a0, rows_out, n_rows);
+}
+
+epp_status epp_generate_trajectory_limited_host(const double* wp, int32_t n_wp, double v_max, double a_max, double dt,
+                                                double t0, const double v0[3], const double a0[3], double** rows_out,
+                                                int64_t* n_rows, double* scale_out) {
+    return generate_scaled(wp, n_wp, v_max, a_max, dt, t0, v0, a0, true, nullptr, rows_out, n_rows, scale_out,
+                           nullptr);
+}
+
+// The same with epp_traj_scale_to_thrust_limits (thrust_scale.hip) after the v / a scaling,
+// which enforce_va switches: one launch more on the same stream, before the one synchronisation.
+epp_status epp_generate_trajectory_flyable_host(const double* wp, int32_t n_wp, double v_max, double a_max, double dt,
+                                                double t0, const double v0[3], const double a0[3], int32_t enforce_va,
+                                                double g, double f_min, double f_max, double rate_max,
+                                                double cos_tilt_min, double** rows_out, int64_t* n_rows,
+                                                double* scale_va, double* scale_thrust) {
+    const double tl[5] = {g, f_min, f_max, rate_max, cos_tilt_min};
+    return generate_scaled(wp, n_wp, v_max, a_max, dt, t0, v0, a0, enforce_va != 0, tl, rows_out, n_rows, scale_va,
+                           scale_thrust);
+}
+
+}  // extern "C"

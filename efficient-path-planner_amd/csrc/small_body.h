@@ -1,5 +1,5 @@
 // small_body.h — device bodies of the brute-force small-query kernels (small.hip), shared
-// with the fused check + refit kernel of the online step (minsnap.hip).  See small.hip.
+// with the fused check + refit kernel of the online step (minsnap_refit.hip).  See small.hip.
 #pragma once
 #include "collision_common.h"
 #include "completion.h"
@@ -48,7 +48,7 @@ __host__ __device__ inline size_t small_shm(int n_obb) { return (((size_t)n_obb 
 
 // The body of k_states_small for logical workgroup `blk` (its queries [blk per, (blk+1)
 // per)), with `srec` the workgroup's dynamic LDS (small_shm bytes).  Also run by the fused
-// check + refit kernel (minsnap.hip, k_check_refit) on the workgroups after the refit's.
+// check + refit kernel (minsnap_refit.hip, k_check_refit) on the workgroups after the refit's.
 template <bool MINDIST, bool COMPACT>
 __device__ __forceinline__ void states_small_body(double* srec, int blk, const double* __restrict__ recs, int n_obb,
                                                   double rg, double ro, const double* __restrict__ xyz, int64_t n,

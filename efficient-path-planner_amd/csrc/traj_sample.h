@@ -1,8 +1,8 @@
 // traj_sample.h — the sampling arithmetic of a fitted trajectory: the evaluateRange time
-// recurrence (RangeIter), the one loop that steps it (range_produce / range_count) and the
-// polynomial evaluation.  Everything that samples a track runs these: the row sampler
-// (minsnap.hip: k_sample_count, k_sample_rows, the host recurrences of the single-track
-// paths), the fused checks (trajcheck.hip: k_traj_check, k_traj_sweep), the derivative sampler
+// recurrence (RangeIter), the one loop that steps it (range_produce / range_count), the
+// polynomial evaluation and the Nfabian segment time.  Everything that samples a track runs
+// these: the row sampler (minsnap.hip: k_sample_count, k_sample_rows), the host recurrences
+// of the single-track paths (minsnap_refit.hip, host_generate.cpp), the fused checks (trajcheck.hip: k_traj_check, k_traj_sweep), the derivative sampler
 // and the thrust / rate walk (thrust_rates.hip) and tests/traj_rows_host.cpp.  One definition,
 // so all produce the same sample times, segments and positions bit for bit.  Plain C++ apart
 // from the HIP qualifiers: a host program may include it without the HIP runtime.
@@ -22,6 +22,17 @@ namespace epp {
 
 constexpr int kPolyCoeffs = 10;  // coefficients per polynomial (mav_trajectory_generation::Polynomial, N = 10)
 constexpr int kRowChunk = 512;   // samples a kernel's lane 0 produces per round (k_sample_rows, k_traj_*: per LDS half)
+
+// One segment's time from its two waypoints.  The host paths (minsnap_refit.hip,
+// host_generate.cpp) run it with the host's libm, as the reference does; the batch fit runs
+// it on the device (solve_track, minsnap_solve.h).
+EPP_TS_FN double nfabian(const double* p, const double* q, double vmax,
+                                          double amax) {
+    // estimateSegmentTimesNfabian — src/vertex.cpp:272-289 (magic 6.5)
+    const double d0 = q[0] - p[0], d1 = q[1] - p[1], d2 = q[2] - p[2];
+    const double distance = sqrt((d0 * d0 + d1 * d1) + d2 * d2);
+    return distance / vmax * 2 * (1.0 + 6.5 * vmax / amax * exp(-distance / vmax * 2));
+}
 
 // Trajectory::evaluateRange control flow — src/trajectory.cpp:81-141.
 struct RangeIter {

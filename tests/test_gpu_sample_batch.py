@@ -21,7 +21,7 @@ are NOT == (3, 12 and 40 segments: max |single - batch| 6.0e-13, 5.9e-13, 8.6e-1
 fits run the same solve_track with different parameters: the batch kernel (k_minsnap) with 64
 threads and the iterative-refinement step, the refit (k_refit) with 256 threads and without
 that step (EPP_REFIT_REFINE, off: it cost 6-7 us of a ~30 us call) -- read in
-csrc/minsnap.hip, whose comment "the same arithmetic, so the same coefficients" speaks of the
+csrc/minsnap_refit.hip, whose comment "the same arithmetic, so the same coefficients" speaks of the
 G workgroups of one refit launch, and now says so.  Making them equal would put the
 refinement back on the latency path, so the test asserts instead that both sides' rows are
 within the bound of the truth evaluated on the batch's coefficients, the single-track rows

@@ -1,5 +1,5 @@
 """GPU parity of the brute-force small-query kernels (small.hip, small_body.h, and the fused
-check of k_check_refit in minsnap.hip) against the CPU oracle, bit for bit, across OBB counts
+check of k_check_refit in minsnap_refit.hip) against the CPU oracle, bit for bit, across OBB counts
 and batch sizes at which that code changes path:
 
   OBB count   1..256 run the small kernels, 257 the index kernels; stage_records copies 150
