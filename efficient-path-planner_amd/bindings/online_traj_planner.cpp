@@ -387,6 +387,35 @@ PYBIND11_MODULE(online_traj_planner, m) {
             },
             py::arg("waypoint_sets"), py::arg("v_max"), py::arg("a_max"), py::arg("limits"))
         .def(
+            "candidate_snap_costs",  // fit (+ descent over the segment times) and snap cost of K waypoint sets (this build)
+            [](const epp::PathPlanner& self, const std::vector<py::object>& waypointSets, double vMax, double aMax,
+               bool optimize) {
+                std::vector<std::vector<Vec3>> sets;
+                for (const auto& o : waypointSets) {
+                    Matrix w = to_matrix(o);
+                    if (w.cols != 3) throw std::invalid_argument("waypoints must be an (n, 3) array");
+                    std::vector<Vec3> wp;
+                    for (size_t i = 0; i < w.rows; ++i) wp.emplace_back(w(i, 0), w(i, 1), w(i, 2));
+                    sets.push_back(std::move(wp));
+                }
+                std::vector<double> costs;
+                std::vector<std::vector<double>> times;
+                {
+                    py::gil_scoped_release release;
+                    self.candidateSnapCosts(sets, vMax, aMax, optimize, costs, &times);
+                }
+                py::array_t<double> c((py::ssize_t)costs.size());
+                for (size_t i = 0; i < costs.size(); ++i) c.mutable_data()[i] = costs[i];
+                py::list ts;
+                for (const auto& t : times) {
+                    py::array_t<double> a((py::ssize_t)t.size());
+                    for (size_t i = 0; i < t.size(); ++i) a.mutable_data()[i] = t[i];
+                    ts.append(a);
+                }
+                return py::make_tuple(c, ts);
+            },
+            py::arg("waypoint_sets"), py::arg("v_max"), py::arg("a_max"), py::arg("optimize") = false)
+        .def(
             "first_hits",  // where every edge s1[i] -> s2[i] is first blocked, and by which OBB (this build)
             [](const epp::PathPlanner& self, const py::object& s1, const py::object& s2, bool canPassGate) {
                 Matrix a = to_matrix(s1), b = to_matrix(s2);

@@ -25,7 +25,7 @@ static py::array_t<double> generate_trajectory(py::array_t<double, py::array::c_
                                                double v_max, double a_max, double sampling_intervall,
                                                double start_time_offset, py::object initial_vel,
                                                py::object initial_acc, bool enforce_limits,
-                                               py::object thrust_limits) {
+                                               py::object thrust_limits, py::object optimize_times) {
     if (waypoints.ndim() != 2 || waypoints.shape(1) != 3)
         throw std::invalid_argument("waypoints must be an (n, 3) array");
     double v0[3] = {0, 0, 0}, a0[3] = {0, 0, 0};
@@ -42,10 +42,34 @@ static py::array_t<double> generate_trajectory(py::array_t<double, py::array::c_
             throw std::invalid_argument("thrustLimits must be (g, f_min, f_max, rate_max, cos_tilt_min)");
         for (int i = 0; i < 5; ++i) tl[i] = a.data()[i];
     }
+    // optimizeTimes = True | (max_iter, h, t_min): the segment times redistributed at constant
+    // duration to lower the snap cost (epp_minsnap_optimize_times) before any scaling;
+    // None / False: the calls below, as before
+    epp_timeopt_params opt = EPP_TIMEOPT_DEFAULTS;
+    bool timeopt = false;
+    if (!optimize_times.is_none()) {
+        if (py::isinstance<py::bool_>(optimize_times)) {
+            timeopt = optimize_times.cast<bool>();
+        } else {
+            auto a = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(optimize_times);
+            if (!a || a.size() != 3) throw std::invalid_argument("optimizeTimes must be True or (max_iter, h, t_min)");
+            if (!(a.data()[0] >= 0.0 && a.data()[0] <= 1e9)) throw std::invalid_argument("optimizeTimes: max_iter");
+            opt.max_iter = (int32_t)a.data()[0];
+            opt.h = a.data()[1];
+            opt.t_min = a.data()[2];
+            timeopt = true;
+        }
+    }
     double* rows = nullptr;
     int64_t n = 0;
     epp_status rc;
-    if (flyable) {
+    if (timeopt) {
+        py::gil_scoped_release release;
+        rc = epp_generate_trajectory_timeopt_host(waypoints.data(), (int32_t)waypoints.shape(0), v_max, a_max,
+                                                  sampling_intervall, start_time_offset, v0, a0, opt,
+                                                  enforce_limits ? 1 : 0, flyable ? tl : nullptr, &rows, &n, nullptr,
+                                                  nullptr, nullptr);
+    } else if (flyable) {
         py::gil_scoped_release release;
         rc = epp_generate_trajectory_flyable_host(waypoints.data(), (int32_t)waypoints.shape(0), v_max, a_max,
                                                   sampling_intervall, start_time_offset, v0, a0, enforce_limits ? 1 : 0,
@@ -122,7 +146,7 @@ PYBIND11_MODULE(polynomial_trajectory, m) {
     m.def("generate_trajectory", &generate_trajectory, py::arg("waypoints"), py::arg("v_max"), py::arg("a_max"),
           py::arg("sampling_intervall"), py::arg("startTimeOffset") = 0.0, py::arg("initialVel") = py::none(),
           py::arg("initialAcc") = py::none(), py::arg("enforceLimits") = false,
-          py::arg("thrustLimits") = py::none());
+          py::arg("thrustLimits") = py::none(), py::arg("optimizeTimes") = py::none());
     m.def("max_velocity_and_acceleration", &max_velocity_and_acceleration, py::arg("waypoints"), py::arg("v_max"),
           py::arg("a_max"), py::arg("initialVel") = py::none(), py::arg("initialAcc") = py::none());
 }

@@ -421,6 +421,87 @@ void PathPlanner::candidateFlyableScales(const std::vector<std::vector<Vec3>>& s
     if (violated) violated->assign(vi.begin(), vi.end());
 }
 
+// The fit of every set and its snap cost (epp_traj_snap_cost), or the descent over its segment
+// times (epp_minsnap_optimize_times) and the result's cost, on one stream, one synchronisation;
+// device block: [wp | T | offsets | fit status | cost0 | cost | iters | status | coeffs].
+void PathPlanner::candidateSnapCosts(const std::vector<std::vector<Vec3>>& sets, double v_max, double a_max,
+                                     bool optimize, std::vector<double>& costs,
+                                     std::vector<std::vector<double>>* times) const {
+    const char* what = "candidateSnapCosts";
+    for (const auto& s : sets)
+        if (s.size() < 2) throw std::invalid_argument("At least two waypoints are required");
+    const size_t n = sets.size();
+    costs.assign(n, 0.0);
+    if (times) times->assign(n, {});
+    if (n == 0) return;
+    auto need = [what](epp_status rc) {
+        if (rc == EPP_ERR_INVALID_ARGUMENT) throw std::invalid_argument(epp_last_error());
+        if (rc != EPP_OK) throw std::runtime_error(std::string(what) + ": " + epp_last_error());
+    };
+    size_t total = 0;
+    for (const auto& s : sets) total += s.size();
+    const size_t nseg = total - n;
+    std::vector<double> wp(total * 3);
+    std::vector<int32_t> off(n + 1, 0);
+    size_t w = 0;
+    for (size_t k = 0; k < n; ++k) {
+        for (const Vec3& p : sets[k]) {
+            wp[3 * w] = p.x;
+            wp[3 * w + 1] = p.y;
+            wp[3 * w + 2] = p.z;
+            ++w;
+        }
+        off[k + 1] = (int32_t)w;
+    }
+    struct Dev {  // released on every way out
+        void* buf = nullptr;
+        void* st = nullptr;
+        ~Dev() {
+            if (st) (void)epp_stream_destroy(st);
+            if (buf) (void)epp_free(buf);
+        }
+    } d;
+    auto after = [](size_t o, size_t b) { return (o + b + 255) & ~(size_t)255; };  // 256-B aligned parts
+    const size_t o_wp = 0, o_T = after(o_wp, total * 24), o_off = after(o_T, nseg * 8),
+                 o_fs = after(o_off, (n + 1) * 4), o_j0 = after(o_fs, n * 4), o_j = after(o_j0, n * 8),
+                 o_it = after(o_j, n * 8), o_st = after(o_it, n * 4), o_C = after(o_st, n * 4),
+                 bytes = after(o_C, nseg * 240);
+    need(epp_malloc(&d.buf, bytes));
+    need(epp_stream_create(&d.st));
+    char* base = static_cast<char*>(d.buf);
+    need(epp_memcpy_h2d_async(base + o_wp, wp.data(), total * 24, d.st));
+    need(epp_memcpy_h2d_async(base + o_off, off.data(), (n + 1) * 4, d.st));
+    const double* d_wp = reinterpret_cast<const double*>(base + o_wp);
+    double* d_T = reinterpret_cast<double*>(base + o_T);
+    double* d_C = reinterpret_cast<double*>(base + o_C);
+    const int32_t* d_off = reinterpret_cast<const int32_t*>(base + o_off);
+    int32_t* d_st = reinterpret_cast<int32_t*>(base + o_st);
+    need(epp_minsnap_batch(d_wp, d_off, (int32_t)n, v_max, a_max, nullptr, nullptr, d_T, d_C,
+                           reinterpret_cast<int32_t*>(base + o_fs), d.st));
+    if (optimize) {
+        const epp_timeopt_params prm = EPP_TIMEOPT_DEFAULTS;
+        need(epp_minsnap_optimize_times(d_wp, d_off, (int32_t)n, nullptr, nullptr, d_T, d_C, prm,
+                                        reinterpret_cast<double*>(base + o_j0), reinterpret_cast<double*>(base + o_j),
+                                        reinterpret_cast<int32_t*>(base + o_it), d_st, d.st));
+    } else {
+        need(epp_traj_snap_cost(d_T, d_C, d_off, (int32_t)n, reinterpret_cast<double*>(base + o_j), d_st, d.st));
+    }
+    std::vector<int32_t> fit(n), st(n);
+    std::vector<double> T(nseg);
+    need(epp_memcpy_d2h_async(fit.data(), base + o_fs, n * 4, d.st));
+    need(epp_memcpy_d2h_async(st.data(), base + o_st, n * 4, d.st));
+    need(epp_memcpy_d2h_async(costs.data(), base + o_j, n * 8, d.st));
+    need(epp_memcpy_d2h_async(T.data(), base + o_T, nseg * 8, d.st));
+    need(epp_stream_sync(d.st));
+    for (size_t k = 0; k < n; ++k)
+        if (fit[k] != 0 || st[k] < 0)
+            throw std::runtime_error("generateTrajectory: the fit of waypoint set " + std::to_string(k) +
+                                     " failed (status " + std::to_string(fit[k] != 0 ? fit[k] : st[k]) + ")");
+    if (times)
+        for (size_t k = 0; k < n; ++k)
+            (*times)[k].assign(T.begin() + (off[k] - (long)k), T.begin() + (off[k + 1] - (long)k - 1));
+}
+
 void PathPlanner::candidateClearances(const std::vector<std::vector<Vec3>>& sets, double v_max, double a_max, double dt,
                                       std::vector<double>& clearance, std::vector<long>* row,
                                       std::vector<double>* time, std::vector<int>* nearest) const {

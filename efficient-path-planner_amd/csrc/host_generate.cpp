@@ -51,9 +51,17 @@ epp_status generate_trajectory(const double* wp, int32_t n_wp, const double* tim
 // (enforce_va: k_traj_scale; tl != NULL: k_traj_thrust_scale under tl = [g, f_min, f_max,
 // rate_max, cos_tilt_min] after it -- epp_generate_trajectory_flyable_host; the limited call
 // is enforce_va with tl == NULL)
+// (opt != NULL: k_time_opt under *opt between the fit and the scalings --
+// epp_generate_trajectory_timeopt_host: uniform scaling keeps the optimised ratios of the
+// segment times, so the order is optimise, then scale; opt_out: [cost0, cost1, iters])
+struct TimeoptOut {
+    double cost0 = 0.0, cost1 = 0.0;
+    int32_t iters = 0;
+};
 epp_status generate_scaled(const double* wp, int32_t n_wp, double v_max, double a_max, double dt, double t0,
                            const double v0[3], const double a0[3], bool enforce_va, const double* tl,
-                           double** rows_out, int64_t* n_rows, double* scale_out, double* scale_thrust) {
+                           double** rows_out, int64_t* n_rows, double* scale_out, double* scale_thrust,
+                           const epp_timeopt_params* opt = nullptr, TimeoptOut* opt_out = nullptr) {
     if (!rows_out || !n_rows || (n_wp > 0 && !wp)) {
         set_error("generateTrajectory: invalid argument");
         return EPP_ERR_INVALID_ARGUMENT;
@@ -73,6 +81,11 @@ epp_status generate_scaled(const double* wp, int32_t n_wp, double v_max, double 
                                                                tl[4], nullptr, nullptr, nullptr, nullptr);
         if (bad) return bad;
     }
+    if (opt) {  // likewise the descent's parameters
+        const epp_status bad = epp_minsnap_optimize_times(nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, *opt,
+                                                          nullptr, nullptr, nullptr, nullptr, nullptr);
+        if (bad) return bad;
+    }
     const int M = n_wp - 1;
     for (int i = 0; i < M; ++i)
         if (!(nfabian(wp + 3 * i, wp + 3 * (i + 1), v_max, a_max) > 0)) {  // CHECK_GT(segment_time, 0)  impl :297
@@ -85,8 +98,8 @@ epp_status generate_scaled(const double* wp, int32_t n_wp, double v_max, double 
         return EPP_ERR_HIP;
     }
     epp_status rc;
-    const size_t nd = (size_t)3 * n_wp + 6 + (size_t)M * 31 + 3;  // doubles before the int32 words
-    hipError_t e = c.ensure(nd * 8 + 24, 0, 0);
+    const size_t nd = (size_t)3 * n_wp + 6 + (size_t)M * 31 + 5;  // doubles before the int32 words
+    hipError_t e = c.ensure(nd * 8 + 32, 0, 0);
     if (e != hipSuccess) return buffers_error(e);
     double* h_wp = c.h_in.as<double>();
     double* h_v0 = h_wp + 3 * n_wp;
@@ -95,8 +108,9 @@ epp_status generate_scaled(const double* wp, int32_t n_wp, double v_max, double 
     double* h_C = h_T + M;
     double* h_scale = h_C + (size_t)M * 30;
     double* h_t0 = h_scale + 2;  // (h_scale: [v / a, thrust])
-    int32_t* h_off = reinterpret_cast<int32_t*>(h_t0 + 1);
-    int32_t* h_st = h_off + 2;  // [fit, scale, thrust scale]
+    double* h_cost = h_t0 + 1;   // [cost0, cost1] of the descent
+    int32_t* h_off = reinterpret_cast<int32_t*>(h_cost + 2);
+    int32_t* h_st = h_off + 2;  // [fit, scale, thrust scale, descent, its iterations]
     std::memcpy(h_wp, wp, (size_t)n_wp * 24);
     for (int k = 0; k < 3; ++k) {
         h_v0[k] = v0 ? v0[k] : 0.0;
@@ -109,7 +123,13 @@ epp_status generate_scaled(const double* wp, int32_t n_wp, double v_max, double 
     h_st[0] = -100;
     h_st[1] = enforce_va ? -100 : 0;
     h_st[2] = tl ? -100 : 0;
+    h_st[3] = opt ? -100 : 0;
+    h_st[4] = 0;
+    h_cost[0] = h_cost[1] = 0.0;
     if ((rc = launch_minsnap_track(h_wp, h_off, M, v_max, a_max, h_v0, h_a0, h_T, h_C, h_st, c.s, "generateTrajectory")))
+        return rc;
+    if (opt && (rc = launch_time_opt_track(h_wp, h_off, M, h_v0, h_a0, h_T, h_C, *opt, h_cost, h_cost + 1, h_st + 4,
+                                           h_st + 3, c.s, "generateTrajectory")))
         return rc;
     if (enforce_va && (rc = epp_traj_scale_to_limits(h_T, h_C, h_off, 1, v_max, a_max, h_scale, h_st + 1, c.s)))
         return rc;
@@ -121,10 +141,12 @@ epp_status generate_scaled(const double* wp, int32_t n_wp, double v_max, double 
         set_error(std::string("generateTrajectory: ") + hipGetErrorString(e));
         return EPP_ERR_HIP;
     }
-    if (h_st[0] != 0 || h_st[1] != 0 || h_st[2] != 0) {
-        set_error(fit_status_message(h_st[0], h_st[1], h_st[2]));
+    // (the descent's 1 -- no step accepted -- and 2 -- max_iter steps taken -- are answers)
+    if (h_st[0] != 0 || h_st[3] < 0 || h_st[1] != 0 || h_st[2] != 0) {
+        set_error(fit_status_message(h_st[0] != 0 ? h_st[0] : h_st[3] < 0 ? h_st[3] : 0, h_st[1], h_st[2]));
         return EPP_ERR_RUNTIME;
     }
+    if (opt_out) *opt_out = TimeoptOut{h_cost[0], h_cost[1], h_st[4]};
     int64_t R = 0;
     if (dt > 0) {  // Trajectory::evaluateRange's recurrence on the scaled times (exact count)
         RangeIter it;
@@ -215,6 +237,24 @@ epp_status epp_generate_trajectory_flyable_host(const double* wp, int32_t n_wp, 
     const double tl[5] = {g, f_min, f_max, rate_max, cos_tilt_min};
     return generate_scaled(wp, n_wp, v_max, a_max, dt, t0, v0, a0, enforce_va != 0, tl, rows_out, n_rows, scale_va,
                            scale_thrust);
+}
+
+// The fit, the descent over its segment times (time_alloc.hip), the scalings asked for, the
+// sampler: one stream, one synchronisation before the row count.
+epp_status epp_generate_trajectory_timeopt_host(const double* wp, int32_t n_wp, double v_max, double a_max, double dt,
+                                                double t0, const double v0[3], const double a0[3],
+                                                epp_timeopt_params params, int32_t enforce_va,
+                                                const double* thrust_limits, double** rows_out, int64_t* n_rows,
+                                                double* cost0, double* cost1, int32_t* iters) {
+    TimeoptOut out;
+    const epp_status rc = generate_scaled(wp, n_wp, v_max, a_max, dt, t0, v0, a0, enforce_va != 0, thrust_limits,
+                                          rows_out, n_rows, nullptr, nullptr, &params, &out);
+    if (rc == EPP_OK) {
+        if (cost0) *cost0 = out.cost0;
+        if (cost1) *cost1 = out.cost1;
+        if (iters) *iters = out.iters;
+    }
+    return rc;
 }
 
 }  // extern "C"

@@ -142,29 +142,6 @@ size_t sample_rows_shm(int max_m) { return ((size_t)kNC + ((max_m + 1) & ~1) + 3
 
 CachedWs g_minsnap_ws[64];
 
-// The track offsets of a batch (they live on the device; the launchers need the largest
-// segment count to size LDS and the total for the global scratch).
-epp_status read_offsets(const int32_t* d_off, int n_tracks, hipStream_t s, const char* what, int* max_m,
-                        int64_t* total_m) {
-    std::vector<int32_t> off(n_tracks + 1);
-    hipError_t e = hipMemcpyAsync(off.data(), d_off, off.size() * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) {
-        set_error(std::string(what) + ": reading track offsets: " + hipGetErrorString(e));
-        return EPP_ERR_HIP;
-    }
-    int m = 1;
-    int64_t tot = 0;
-    for (int t = 0; t < n_tracks; ++t) {
-        const int mt = off[t + 1] - off[t] - 1;
-        m = std::max(m, mt);
-        tot += std::max(0, mt);
-    }
-    *max_m = m;
-    if (total_m) *total_m = tot;
-    return EPP_OK;
-}
-
 epp_status minsnap_batch(const double* wp, const int32_t* wp_offsets, int32_t n_tracks, double v_max, double a_max,
                          const double* v0, const double* a0, const double* times_in, double* seg_times, double* coeffs,
                          int32_t* status, void* stream, const char* what, int known_m = -1) {
@@ -226,6 +203,29 @@ epp_status minsnap_batch(const double* wp, const int32_t* wp_offsets, int32_t n_
 }
 
 }  // namespace
+
+// The track offsets of a batch (they live on the device; the launchers need the largest
+// segment count to size LDS and the total for the global scratch; minsnap_kernels.h).
+epp_status read_offsets(const int32_t* d_off, int n_tracks, hipStream_t s, const char* what, int* max_m,
+                        int64_t* total_m) {
+    std::vector<int32_t> off(n_tracks + 1);
+    hipError_t e = hipMemcpyAsync(off.data(), d_off, off.size() * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        set_error(std::string(what) + ": reading track offsets: " + hipGetErrorString(e));
+        return EPP_ERR_HIP;
+    }
+    int m = 1;
+    int64_t tot = 0;
+    for (int t = 0; t < n_tracks; ++t) {
+        const int mt = off[t + 1] - off[t] - 1;
+        m = std::max(m, mt);
+        tot += std::max(0, mt);
+    }
+    *max_m = m;
+    if (total_m) *total_m = tot;
+    return EPP_OK;
+}
 
 epp_status launch_minsnap_track(const double* wp, const int32_t* wp_off, int M, double v_max, double a_max,
                                 const double* v0, const double* a0, double* seg_times, double* coeffs,

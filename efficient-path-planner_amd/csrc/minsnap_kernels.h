@@ -10,6 +10,8 @@
 //   minsnap_refit.hip   the 50 Hz latency path: one track fitted and sampled in one launch
 //                       (k_refit, k_check_refit) behind generate_trajectory_into /
 //                       check_and_generate_into (epp_internal.h)
+//   time_alloc.hip      snap cost, Mellinger gradient and descent over the segment times
+//                       (time_alloc.h: the arithmetic they share with the host)
 //   host_generate.cpp   the C entry points of the single-track host calls, and the fits
 //                       scaled to limits (fit, scale kernels, sampler on one stream)
 //
@@ -19,6 +21,7 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 
+#include "epp.h"
 #include "epp_internal.h"
 
 namespace epp {
@@ -34,6 +37,17 @@ epp_status launch_minsnap_track(const double* wp, const int32_t* wp_off, int M, 
 epp_status launch_sample_rows_track(const double* seg_times, const double* coeffs, const int32_t* wp_off, int M,
                                     double dt, const double* t0, double* rows, int64_t cap_rows, hipStream_t st,
                                     const char* what);
+
+// (minsnap.hip) the track offsets of a batch read back from the device on s: the largest
+// segment count (at least 1) and, total_m != NULL, the total
+epp_status read_offsets(const int32_t* d_off, int n_tracks, hipStream_t s, const char* what, int* max_m,
+                        int64_t* total_m);
+
+// (time_alloc.hip) k_time_opt over one track of M segments in place on seg_times / coeffs (the
+// host caller knows M); as epp_minsnap_optimize_times otherwise, its argument checks included
+epp_status launch_time_opt_track(const double* wp, const int32_t* wp_off, int M, const double* v0, const double* a0,
+                                 double* seg_times, double* coeffs, const epp_timeopt_params& p, double* cost0,
+                                 double* cost1, int32_t* iters, int32_t* status, hipStream_t st, const char* what);
 
 // The error text of a single-track call from its kernels' statuses: the fit's (-2: a segment
 // time <= 0, the reference's CHECK_GT(segment_time, 0), impl :297; else the solve), then the

@@ -109,6 +109,13 @@ def lib() -> C.CDLL:
             "epp_traj_thrust_rates_batch": (i32, [vp, vp, vp, i32, dp, dp, vp, vp, vp]),
             "epp_traj_thrust_grid_batch": (i32, [vp, vp, vp, i32, vp, dp, vp, vp]),
             "epp_traj_scale_to_thrust_limits": (i32, [vp, vp, vp, i32, dp, dp, dp, dp, dp, vp, vp, vp, vp]),
+            "epp_traj_snap_cost": (i32, [vp, vp, vp, i32, vp, vp, vp]),
+            "epp_minsnap_time_gradient": (i32, [vp, vp, i32, vp, vp, vp, dp, dp, vp, vp, vp, vp]),
+            "epp_minsnap_optimize_times": (i32, [vp, vp, i32, vp, vp, vp, vp, TimeoptParams, vp, vp, vp, vp, vp]),
+            "epp_generate_trajectory_timeopt_host": (i32, [vp, i32, dp, dp, dp, dp, vp, vp, TimeoptParams, i32, vp,
+                                                           C.POINTER(C.POINTER(C.c_double)), C.POINTER(i64),
+                                                           C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                           C.POINTER(i32)]),
             "epp_generate_trajectory_flyable_host": (i32, [vp, i32, dp, dp, dp, dp, vp, vp, i32, dp, dp, dp, dp, dp,
                                                            C.POINTER(C.POINTER(C.c_double)), C.POINTER(i64),
                                                            C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -179,7 +186,18 @@ EXPORTED = [
     "epp_motions_first_hit", "epp_traj_first_hit_batch", "epp_gates_crossed", "epp_traj_gate_pass_batch",
     "epp_sample_derivative_batch", "epp_thrust_rates", "epp_traj_thrust_rates_batch", "epp_device_cu_count",
     "epp_traj_thrust_grid_batch", "epp_traj_scale_to_thrust_limits", "epp_generate_trajectory_flyable_host",
+    "epp_traj_snap_cost", "epp_minsnap_time_gradient", "epp_minsnap_optimize_times",
+    "epp_generate_trajectory_timeopt_host",
 ]
+
+
+class TimeoptParams(C.Structure):
+    """epp_timeopt_params (include/epp.h); the defaults are EPP_TIMEOPT_DEFAULTS."""
+    _fields_ = [("h", C.c_double), ("t_min", C.c_double), ("step0", C.c_double), ("max_halvings", C.c_int32),
+                ("ftol", C.c_double), ("max_iter", C.c_int32)]
+
+    def __init__(self, h=0.1, t_min=0.1, step0=0.5, max_halvings=8, ftol=1e-4, max_iter=20):
+        super().__init__(float(h), float(t_min), float(step0), int(max_halvings), float(ftol), int(max_iter))
 
 
 def check(rc: int) -> None:
@@ -789,6 +807,94 @@ def scale_to_thrust_limits(Ts, Cs, g, f_min, f_max, rate_max, cos_tilt_min):
         Tn.append(T[a:max(a, b)])
         Cn.append(Cf[a:max(a, b)])
     return Tn, Cn, d_sc.download(np.float64, nt), d_st.download(np.int32, nt), d_vi.download(np.int32, nt)
+
+
+def snap_cost(Ts, Cs):
+    """epp_traj_snap_cost on the lists minsnap_batch returns: (cost array, status array)."""
+    nt = len(Ts)
+    d_T, d_C, d_off, _, _ = _upload_tracks(Ts, Cs)
+    d_J, d_st = DeviceBuffer(8 * max(nt, 1)), DeviceBuffer(4 * max(nt, 1))
+    check(lib().epp_traj_snap_cost(d_T.ptr, d_C.ptr, d_off.ptr, nt, d_J.ptr, d_st.ptr, None))
+    sync()
+    return d_J.download(np.float64, nt), d_st.download(np.int32, nt)
+
+
+def _upload_fit_inputs(tracks, times, v0, a0):
+    wp = np.ascontiguousarray(np.concatenate([np.asarray(t, np.float64).reshape(-1, 3) for t in tracks]))
+    off = np.zeros(len(tracks) + 1, np.int32)
+    off[1:] = np.cumsum([len(np.asarray(t).reshape(-1, 3)) for t in tracks])
+    nseg = int(off[-1]) - len(tracks)
+    T = np.ascontiguousarray(np.concatenate([np.asarray(t, np.float64).ravel() for t in times] + [np.zeros(0)]))
+    assert len(T) == nseg
+    d_wp, d_off = DeviceBuffer.from_array(wp), DeviceBuffer.from_array(off)
+    d_T = DeviceBuffer.from_array(T if nseg else np.zeros(1))
+    d_v0 = DeviceBuffer.from_array(np.ascontiguousarray(v0, np.float64)) if v0 is not None else None
+    d_a0 = DeviceBuffer.from_array(np.ascontiguousarray(a0, np.float64)) if a0 is not None else None
+    return d_wp, d_off, d_T, d_v0, d_a0, off, nseg
+
+
+def time_gradient(tracks, times, h=0.1, t_min=0.1, v0=None, a0=None):
+    """epp_minsnap_time_gradient: the snap cost of the fit at the caller's segment times (a list
+    of (W_k - 1) arrays) and its Mellinger gradient.  Returns (cost array, grad list, status
+    array)."""
+    nt = len(tracks)
+    d_wp, d_off, d_T, d_v0, d_a0, off, nseg = _upload_fit_inputs(tracks, times, v0, a0)
+    d_J, d_g, d_st = DeviceBuffer(8 * nt), DeviceBuffer(8 * max(nseg, 1)), DeviceBuffer(4 * nt)
+    check(lib().epp_minsnap_time_gradient(d_wp.ptr, d_off.ptr, nt, d_v0.ptr if d_v0 else None,
+                                          d_a0.ptr if d_a0 else None, d_T.ptr, float(h), float(t_min), d_J.ptr,
+                                          d_g.ptr, d_st.ptr, None))
+    sync()
+    g = d_g.download(np.float64, nseg)
+    return (d_J.download(np.float64, nt), [g[int(off[k]) - k:max(int(off[k]) - k, int(off[k + 1]) - k - 1)]
+                                           for k in range(nt)], d_st.download(np.int32, nt))
+
+
+def optimize_times(tracks, times, params=None, v0=None, a0=None):
+    """epp_minsnap_optimize_times from the caller's segment times.  params: a TimeoptParams
+    (None: the defaults).  Returns (seg_times list, coeffs list, cost0, cost1, iters, status)."""
+    nt = len(tracks)
+    d_wp, d_off, d_T, d_v0, d_a0, off, nseg = _upload_fit_inputs(tracks, times, v0, a0)
+    d_C = DeviceBuffer(240 * max(nseg, 1))
+    d_C.zero()
+    d_J0, d_J1, d_it, d_st = DeviceBuffer(8 * nt), DeviceBuffer(8 * nt), DeviceBuffer(4 * nt), DeviceBuffer(4 * nt)
+    check(lib().epp_minsnap_optimize_times(d_wp.ptr, d_off.ptr, nt, d_v0.ptr if d_v0 else None,
+                                           d_a0.ptr if d_a0 else None, d_T.ptr, d_C.ptr,
+                                           params if params is not None else TimeoptParams(), d_J0.ptr, d_J1.ptr,
+                                           d_it.ptr, d_st.ptr, None))
+    sync()
+    T = d_T.download(np.float64, nseg)
+    Cf = d_C.download(np.float64, nseg * 30).reshape(nseg, 3, 10)
+    Tn, Cn = [], []
+    for k in range(nt):
+        a, b = int(off[k]) - k, int(off[k + 1]) - k - 1
+        Tn.append(T[a:max(a, b)])
+        Cn.append(Cf[a:max(a, b)])
+    return (Tn, Cn, d_J0.download(np.float64, nt), d_J1.download(np.float64, nt), d_it.download(np.int32, nt),
+            d_st.download(np.int32, nt))
+
+
+def generate_trajectory_timeopt(waypoints, v_max, a_max, dt, params=None, t0=0.0, v0=(0, 0, 0), a0=(0, 0, 0),
+                                enforce_va=False, limits=None, return_costs=False):
+    """epp_generate_trajectory_timeopt_host: generate_trajectory with the segment times
+    optimised (epp_minsnap_optimize_times under params, None: the defaults), then scaled to
+    v_max / a_max when enforce_va and to limits = (g, f_min, f_max, rate_max, cos_tilt_min) when
+    given.  return_costs: (rows, cost0, cost1, iters)."""
+    wp = np.ascontiguousarray(np.asarray(waypoints, np.float64).reshape(-1, 3))
+    v0 = np.ascontiguousarray(v0, np.float64)
+    a0 = np.ascontiguousarray(a0, np.float64)
+    tl = np.ascontiguousarray(limits, np.float64) if limits is not None else None
+    rows = C.POINTER(C.c_double)()
+    n = C.c_int64(0)
+    j0, j1, it = C.c_double(0.0), C.c_double(0.0), C.c_int32(0)
+    check(lib().epp_generate_trajectory_timeopt_host(_ptr(wp), len(wp), float(v_max), float(a_max), float(dt),
+                                                     float(t0), _ptr(v0), _ptr(a0),
+                                                     params if params is not None else TimeoptParams(),
+                                                     1 if enforce_va else 0, _ptr(tl) if tl is not None else None,
+                                                     C.byref(rows), C.byref(n), C.byref(j0), C.byref(j1),
+                                                     C.byref(it)))
+    out = np.ctypeslib.as_array(rows, shape=(n.value * 10,)).copy().reshape(-1, 10) if n.value else np.zeros((0, 10))
+    lib().epp_host_free(C.cast(rows, C.c_void_p))
+    return (out, j0.value, j1.value, it.value) if return_costs else out
 
 
 def generate_trajectory_flyable(waypoints, v_max, a_max, dt, limits, t0=0.0, v0=(0, 0, 0), a0=(0, 0, 0),

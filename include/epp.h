@@ -55,6 +55,11 @@
  *       Trajectory::scaleSegmentTimesToMeetConstraints (external/poly_traj/src/trajectory.cpp:
  *       385-429) extended from |v| and |a| to thrust, body-rate and tilt limits: the extremes
  *       over the peak search's grid points at a scale, and the search for the scale.
+ *   epp_traj_snap_cost / epp_minsnap_time_gradient / epp_minsnap_optimize_times
+ *       PolynomialOptimization::computeCost (impl/polynomial_optimization_linear_impl.h:123-140),
+ *       getCostAndGradientMellinger (impl/polynomial_optimization_nonlinear_impl.h:286-364, which
+ *       the reference ships commented out: its optimiser is NLopt) and a projected descent over
+ *       the segment times at constant total time in its place.
  */
 #ifndef EPP_H_
 #define EPP_H_
@@ -534,6 +539,67 @@ epp_status epp_traj_scale_to_thrust_limits(double* seg_times, double* coeffs, co
                                            double cos_tilt_min, double* scale, int32_t* status, int32_t* violated,
                                            void* stream);
 
+/* ---- segment-time allocation (device pointers) ------------------------------------- */
+/* PolynomialOptimization::computeCost (impl/polynomial_optimization_linear_impl.h:123-140) of
+ * every track of a batch in the layout of epp_minsnap_batch, from its coefficients:
+ *   cost[k] = 0.5 * sum_seg sum_dim c^T Q(T) c,
+ *   Q[a][b] = B4[a] B4[b] T^(a+b-7) 2 / (a+b-7) for a, b >= 4, else 0, B4[j] = j! / (j-4)!
+ * (computeQuadraticCostJacobian, impl :567-583, derivative 4): the integral of the squared
+ * snap over the track.  The order of the arithmetic is csrc/time_alloc.h's.  status (n_tracks,
+ * may be NULL): 0 ok; -1 as epp_traj_peaks (no segment, a segment time <= 0 or non-finite
+ * input): cost NaN. */
+epp_status epp_traj_snap_cost(const double* seg_times, const double* coeffs, const int32_t* wp_offsets,
+                              int32_t n_tracks, double* cost, int32_t* status, void* stream);
+/* getCostAndGradientMellinger (impl/polynomial_optimization_nonlinear_impl.h:286-364) of every
+ * track at the caller's segment times: cost[k] = J(T), the cost above of the fit at T
+ * (epp_minsnap_batch_times), and for every segment n (grad: total segments)
+ *   grad[n] = (J(T^(n)) - J(T)) / h,
+ *   T^(n)_i = max(t_min, T_i + h) for i = n, max(t_min, T_i - h / (M - 1)) for i != n:
+ * a directional difference at constant total time, except that the clamp may change the
+ * total; the quotient divides by h all the same, as the reference does (its h and t_min are
+ * both 0.1).  A track of one segment has gradient 0.  One workgroup per (track, variant):
+ * sum (M + 1) independent solves in one launch.  status (n_tracks, may be NULL): the fit's at
+ * T (0, -1, -2, -3: cost and gradient NaN), else -3 when a variant's solve broke down (its
+ * gradient entry is NaN).  EPP_ERR_INVALID_ARGUMENT for h <= 0 or t_min <= 0 (or NaN). */
+epp_status epp_minsnap_time_gradient(const double* wp, const int32_t* wp_offsets, int32_t n_tracks,
+                                     const double* v0, const double* a0, const double* seg_times, double h,
+                                     double t_min, double* cost, double* grad, int32_t* status, void* stream);
+/* The parameters of epp_minsnap_optimize_times.  h and t_min are the reference's
+ * (increment_time and kOptimizationTimeLowerBound, both 0.1); step0, max_halvings, ftol and
+ * max_iter are this library's choices: the reference hands the iteration to NLopt. */
+typedef struct epp_timeopt_params {
+    double h;              /* the gradient's increment, > 0 */
+    double t_min;          /* lower bound of every segment time, > 0 */
+    double step0;          /* first step: the shortest segment changes by at most this part, in (0, 1] */
+    int32_t max_halvings;  /* halvings of a rejected step, >= 0 */
+    double ftol;           /* stop when a step lowers the cost by <= ftol * cost, >= 0 */
+    int32_t max_iter;      /* accepted steps at most, >= 0 */
+} epp_timeopt_params;
+#define EPP_TIMEOPT_DEFAULTS {0.1, 0.1, 0.5, 8, 1e-4, 20}
+/* Redistributes every track's duration over its segments to lower the snap cost, the total
+ * kept: the outer loop of Mellinger's time allocation, the whole loop of a track in one
+ * launch (one workgroup per track, its solves one after another; the batch is the
+ * parallelism).  seg_times: in the start, out the result; coeffs (out): the fit at the result,
+ * bit for bit epp_minsnap_batch_times there.  Per iteration, with J and g as
+ * epp_minsnap_time_gradient(h, t_min) gives them at T:
+ *   d_i = g_i - (sum_{n != i} g_n) / (M - 1)        (sums to 0: the total is kept)
+ *   stop, status 0, when max_i |d_i| == 0; stop, status 1, when some d_i is not finite
+ *   alpha = step0 * min_i T_i / max_i |d_i|
+ *   try T' = T - alpha d, at most 1 + max_halvings times, alpha halved after each failure,
+ *   until every T'_i >= t_min and J(T') < J(T); none accepted: stop, status 1
+ *   T = T'; stop, status 0, when J(T) - J(T') <= ftol * J(T)
+ * and status 2 after max_iter accepted steps.  Then T is multiplied by (starting sum) / (sum
+ * of T), both sums in order, and fitted once more: that solve's coefficients and cost are the
+ * outputs.  cost0 / cost1 (n_tracks): the cost at the start and of the result; iters: the
+ * accepted steps.  A track of one segment, max_iter == 0 and a track whose first fit fails
+ * or is not finite return the plain fit at the given times: cost1 == cost0, iters 0, status
+ * the fit's (0, -1, -2, -3).  EPP_ERR_INVALID_ARGUMENT for h <= 0, t_min <= 0, step0 outside
+ * (0, 1], ftol < 0 (or NaN), max_halvings < 0 or max_iter < 0. */
+epp_status epp_minsnap_optimize_times(const double* wp, const int32_t* wp_offsets, int32_t n_tracks,
+                                      const double* v0, const double* a0, double* seg_times, double* coeffs,
+                                      epp_timeopt_params params, double* cost0, double* cost1, int32_t* iters,
+                                      int32_t* status, void* stream);
+
 /* ---- batch planner building blocks (device pointers) ------------------------------- */
 /* Replace OMPL's sampler / nearest-neighbour structure behind PathPlanner::planPath
  * (src/PathPlanner.cpp:80-158).  Counter-based uniform states in [lo, hi]:
@@ -687,6 +753,19 @@ epp_status epp_generate_trajectory_flyable_host(const double* wp, int32_t n_wp, 
                                                 int32_t enforce_va, double g, double f_min, double f_max,
                                                 double rate_max, double cos_tilt_min, double** rows,
                                                 int64_t* n_rows, double* scale_va, double* scale_thrust);
+/* epp_generate_trajectory_host with the segment times optimised before anything else: the
+ * Nfabian fit, epp_minsnap_optimize_times under `params`, then -- uniform scaling keeps the
+ * optimised ratios -- epp_traj_scale_to_limits when enforce_va != 0 and
+ * epp_traj_scale_to_thrust_limits when thrust_limits ([g, f_min, f_max, rate_max,
+ * cos_tilt_min], may be NULL) is given, then the sampling; one stream, launches over pinned
+ * host buffers as epp_generate_trajectory_limited_host.  *cost0, *cost1, *iters (may be NULL):
+ * the descent's.  Errors as epp_generate_trajectory_flyable_host and
+ * epp_minsnap_optimize_times. */
+epp_status epp_generate_trajectory_timeopt_host(const double* wp, int32_t n_wp, double v_max, double a_max,
+                                                double dt, double t0, const double v0[3], const double a0[3],
+                                                epp_timeopt_params params, int32_t enforce_va,
+                                                const double* thrust_limits, double** rows, int64_t* n_rows,
+                                                double* cost0, double* cost1, int32_t* iters);
 /* The C5 online step's two GPU calls in ONE launch (an addition of this build; the
  * reference makes them one after the other: PathPlanner::checkTrajectoryValidity,
  * src/PathPlanner.cpp:267-280, then poly_traj::generateTrajectory, src/

@@ -204,6 +204,16 @@ public:
     void candidateFlyableScales(const std::vector<std::vector<Vec3>>& waypointSets, double v_max, double a_max,
                                 const FlightLimits& limits, std::vector<double>& scale, std::vector<double>& duration,
                                 std::vector<int>& status, std::vector<int>* violated = nullptr) const;
+    // The snap cost of each of K candidate waypoint sets' trajectories (an addition of this
+    // build), to rank candidates by smoothness: the fit of every set as above and, on the same
+    // stream with one synchronisation, epp_traj_snap_cost (include/epp.h) of the fit; with
+    // `optimize`, epp_minsnap_optimize_times (default parameters) from the fit's Nfabian times
+    // first, and the cost of its result.  costs[k]: PolynomialOptimization::computeCost, the
+    // integral of the squared snap; times (optional): the K sets' segment times, the optimised
+    // ones with `optimize` (their sums are the fits').  Throws as candidateThrustRates.
+    void candidateSnapCosts(const std::vector<std::vector<Vec3>>& waypointSets, double v_max, double a_max,
+                            bool optimize, std::vector<double>& costs,
+                            std::vector<std::vector<double>>* times = nullptr) const;
     std::vector<Vec3> includeGates2(std::vector<std::vector<Vec3>> waypoints) const;
     // planPaths of consecutive gate-to-gate segments, then includeGates2 of their paths (an
     // addition of this build, for OnlineTrajGenerator::preComputeTraj): the same answers as
