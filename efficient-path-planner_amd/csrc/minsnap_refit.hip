@@ -58,7 +58,7 @@ __host__ __device__ inline size_t refit_nin_even(int W) { return ((size_t)3 * W 
 // LDS doubles: flag (2) | constants | wp, v0, a0, T | solve scratch | coefficients |
 // sample chunk (t_in, t, segment) | row chunk.  big: the vertex values, right-hand sides,
 // times and coefficients live in the global scratch; LDS keeps the lane exchange (kXch).
-// (A refit workgroup's dynamic LDS stays within kLdsBudget, of 160 KB per CU.)
+// (A refit workgroup's dynamic LDS stays within kLdsBudget, 150 KB, of the 160 KB a CU has.)
 __host__ __device__ inline size_t refit_lds_doubles(int M, bool lds, bool big = false) {
     return 2 + kNC + refit_nin_even(M + 1) + (lds ? (size_t)M * Seg::kSize : 0) +
            (big ? (size_t)kXch : vertex_doubles(M) + (size_t)M * 30) + (size_t)kRefitRowChunk * 3 + 2 +
@@ -263,7 +263,7 @@ epp_status refit_host_side(RefitCache& c, const FusedCheck* chk, const double* w
     const int R = (int)c.tin.size();
     const bool lds = M <= kMaxLdsSeg;
     // long tracks whose vertex values and coefficients would not fit LDS beside the rest
-    // (> ~300 segments: e.g. a track smoothed by "ompl" simplification) keep them in the
+    // (from 276 segments: e.g. a track smoothed by "ompl" simplification) keep them in the
     // global scratch too
     const bool big = !lds && refit_lds_doubles(M, false) * sizeof(double) > kLdsBudget;
     if (refit_lds_doubles(M, lds, big) * sizeof(double) > kLdsBudget) {

@@ -32,9 +32,11 @@ def test_golden_tracks():
         assert np.abs(Cf - np.array(t["coeffs"])).max() < COEF_TOL
 
 
-@pytest.mark.parametrize("n_seg", [1, 2, 5, 12, 24, 25, 40])
+@pytest.mark.parametrize("n_seg", [1, 2, 5, 12, 24, 25, 40, 41])
 def test_batch_vs_oracle(n_seg):
-    """12 segments = BASELINE config 5; > 24 segments runs the global-scratch kernel."""
+    """12 segments = BASELINE config 5; > 40 segments (kMaxLdsSeg, csrc/minsnap_solve.h) runs the
+    global-scratch kernel.  Nothing changes at 24: it was the limit while the kernel kept to the
+    64 KB of LDS a launch gets without opting in to more."""
     tracks = [synth.random_track_waypoints(300 + 17 * n_seg + k, n_seg) for k in range(16)]
     rs = np.random.RandomState(n_seg)
     v0 = rs.uniform(-0.5, 0.5, (16, 3))
@@ -92,7 +94,7 @@ def test_generate_trajectory_vs_oracle(seed):
                                   (800, 0.1), (2000, 0.2)])
 def test_generate_trajectory_long_tracks(n, dt):
     """The single-track latency path: up to 40 segments in LDS; more: the segment scratch
-    in global memory; past ~300 segments (e.g. a track smoothed by "ompl" simplification:
+    in global memory; from 276 segments (e.g. a track smoothed by "ompl" simplification:
     ~330 waypoints) the vertex values and coefficients too ("big" refit); many rows (row
     buffer sized from host-side segment times)."""
     wp = synth.random_track_waypoints(900 + n, n)
