@@ -9,6 +9,7 @@
 #include <cstring>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "epp.h"
 
@@ -21,16 +22,78 @@ static void read3(py::object o, double* out) {
     for (int i = 0; i < 3; ++i) out[i] = a.data()[i];
 }
 
+// waypointVel / waypointAcc: a list as long as the waypoints, None = free there; derivative k of
+// the inner waypoints it names goes into mask / values (epp_minsnap_batch_constrained's layout)
+static void read_waypoint_pins(py::object o, int k, py::ssize_t n, std::vector<uint8_t>& mask,
+                               std::vector<double>& values, const char* name) {
+    if (o.is_none()) return;
+    if (!py::isinstance<py::sequence>(o) || (py::ssize_t)py::len(o) != n)
+        throw py::value_error(std::string(name) + " needs one entry (a 3-vector or None) per waypoint");
+    py::sequence seq = py::reinterpret_borrow<py::sequence>(o);
+    for (py::ssize_t w = 0; w < n; ++w) {
+        py::object e = seq[w];
+        if (e.is_none()) continue;
+        if (w == 0 || w == n - 1)
+            throw py::value_error(std::string(name) + ": the first and the last waypoint take initialVel / "
+                                  "initialAcc and finalVel / finalAcc");
+        mask[w] |= (uint8_t)(1u << (k - 1));
+        read3(e, &values[((size_t)w * 4 + (k - 1)) * 3]);
+    }
+}
+
 static py::array_t<double> generate_trajectory(py::array_t<double, py::array::c_style | py::array::forcecast> waypoints,
                                                double v_max, double a_max, double sampling_intervall,
                                                double start_time_offset, py::object initial_vel,
                                                py::object initial_acc, bool enforce_limits,
-                                               py::object thrust_limits, py::object optimize_times) {
+                                               py::object thrust_limits, py::object optimize_times,
+                                               py::object final_vel, py::object final_acc, py::object initial_jerk,
+                                               py::object initial_snap, py::object waypoint_vel,
+                                               py::object waypoint_acc) {
     if (waypoints.ndim() != 2 || waypoints.shape(1) != 3)
         throw std::invalid_argument("waypoints must be an (n, 3) array");
     double v0[3] = {0, 0, 0}, a0[3] = {0, 0, 0};
     read3(initial_vel, v0);
     read3(initial_acc, a0);
+    // finalVel / finalAcc, initialJerk / initialSnap, waypointVel / waypointAcc: the fit under
+    // these constraints (epp_generate_trajectory_constrained_host); none given: the calls
+    // below, as before.  The time scalings and the time descent do not keep them (scaling
+    // divides a pinned velocity by s, the descent refits without the pins), so the
+    // combinations are refused.
+    if (!(final_vel.is_none() && final_acc.is_none() && initial_jerk.is_none() && initial_snap.is_none() &&
+          waypoint_vel.is_none() && waypoint_acc.is_none())) {
+        const bool timeopt_asked = !optimize_times.is_none() &&
+                                   !(py::isinstance<py::bool_>(optimize_times) && !optimize_times.cast<bool>());
+        if (enforce_limits || !thrust_limits.is_none() || timeopt_asked)
+            throw py::value_error("generate_trajectory: finalVel, finalAcc, initialJerk, initialSnap, waypointVel and "
+                                  "waypointAcc do not combine with enforceLimits, thrustLimits or optimizeTimes");
+        const py::ssize_t n = waypoints.shape(0);
+        if (n < 2) throw std::invalid_argument("At least two waypoints are required");
+        std::vector<uint8_t> mask((size_t)n, 0);
+        std::vector<double> values((size_t)n * 12, 0.0);
+        std::memcpy(&values[0], v0, sizeof(v0));
+        std::memcpy(&values[3], a0, sizeof(a0));
+        read3(initial_jerk, &values[6]);
+        read3(initial_snap, &values[9]);
+        read3(final_vel, &values[(size_t)(n - 1) * 12]);
+        read3(final_acc, &values[(size_t)(n - 1) * 12 + 3]);
+        read_waypoint_pins(waypoint_vel, 1, n, mask, values, "waypointVel");
+        read_waypoint_pins(waypoint_acc, 2, n, mask, values, "waypointAcc");
+        double* rows = nullptr;
+        int64_t nr = 0;
+        epp_status rc;
+        {
+            py::gil_scoped_release release;
+            rc = epp_generate_trajectory_constrained_host(waypoints.data(), (int32_t)n, v_max, a_max, nullptr,
+                                                          sampling_intervall, start_time_offset, mask.data(),
+                                                          values.data(), &rows, &nr);
+        }
+        if (rc == EPP_ERR_INVALID_ARGUMENT) throw std::invalid_argument(epp_last_error());
+        if (rc != EPP_OK) throw std::runtime_error(epp_last_error());
+        py::array_t<double> out({(py::ssize_t)nr, (py::ssize_t)10});
+        if (nr) std::memcpy(out.mutable_data(), rows, (size_t)nr * 10 * sizeof(double));
+        epp_host_free(rows);
+        return out;
+    }
     // thrustLimits = (g, f_min, f_max, rate_max, cos_tilt_min): the fit also time-scaled until
     // its thrust, body rate and tilt are within them (epp_traj_scale_to_thrust_limits),
     // independently of enforceLimits; None: the calls below, as before
@@ -146,7 +209,10 @@ PYBIND11_MODULE(polynomial_trajectory, m) {
     m.def("generate_trajectory", &generate_trajectory, py::arg("waypoints"), py::arg("v_max"), py::arg("a_max"),
           py::arg("sampling_intervall"), py::arg("startTimeOffset") = 0.0, py::arg("initialVel") = py::none(),
           py::arg("initialAcc") = py::none(), py::arg("enforceLimits") = false,
-          py::arg("thrustLimits") = py::none(), py::arg("optimizeTimes") = py::none());
+          py::arg("thrustLimits") = py::none(), py::arg("optimizeTimes") = py::none(), py::kw_only(),
+          py::arg("finalVel") = py::none(), py::arg("finalAcc") = py::none(), py::arg("initialJerk") = py::none(),
+          py::arg("initialSnap") = py::none(), py::arg("waypointVel") = py::none(),
+          py::arg("waypointAcc") = py::none());
     m.def("max_velocity_and_acceleration", &max_velocity_and_acceleration, py::arg("waypoints"), py::arg("v_max"),
           py::arg("a_max"), py::arg("initialVel") = py::none(), py::arg("initialAcc") = py::none());
 }

@@ -1,6 +1,7 @@
 // host_generate.cpp — the C entry points of the single-track host calls: generateTrajectory
 // (and its variants with caller times and with the fused check) over the refit
-// (minsnap_refit.hip), and the fits scaled to limits before the sampling (generate_scaled).
+// (minsnap_refit.hip), the fits scaled to limits before the sampling (generate_scaled) and the
+// fit under the caller's constraints (generate_constrained).
 // Host code only: the kernels are enqueued through minsnap_kernels.h and the C ABI.
 #include <algorithm>
 #include <cstdlib>
@@ -181,6 +182,101 @@ epp_status generate_scaled(const double* wp, int32_t n_wp, double v_max, double 
     return EPP_OK;
 }
 
+// generateTrajectory under the caller's constraints: the constrained batch fit
+// (k_minsnap_constrained, one track) and, after the host has run evaluateRange's sample
+// recurrence on the fit's times to size the row buffer, the row sampler -- two launches on
+// the calling thread's stream over pinned host buffers, as generate_scaled.  times: the
+// caller's segment times (NULL: Nfabian).
+epp_status generate_constrained(const double* wp, int32_t n_wp, double v_max, double a_max, const double* times,
+                                double dt, double t0, const uint8_t* fixed_mask, const double* fixed_val,
+                                double** rows_out, int64_t* n_rows) {
+    if (!rows_out || !n_rows || (n_wp > 0 && (!wp || !fixed_mask || !fixed_val))) {
+        set_error("generateTrajectory: invalid argument");
+        return EPP_ERR_INVALID_ARGUMENT;
+    }
+    *rows_out = nullptr;
+    *n_rows = 0;
+    if (n_wp < 2) {
+        set_error("At least two waypoints are required");  // trajectory_generator.cpp:24
+        return EPP_ERR_INVALID_ARGUMENT;
+    }
+    const int M = n_wp - 1;
+    static thread_local StreamBufs c;
+    if (c.bind() != hipSuccess) {
+        set_error("generateTrajectory: stream");
+        return EPP_ERR_HIP;
+    }
+    epp_status rc;
+    // doubles [wp (3 W) | values (12 W) | T in (M) | T (M) | coeffs (30 M) | t0], then the int32
+    // words [offsets (2) | fit status], then the mask bytes
+    const size_t nd = (size_t)15 * n_wp + (size_t)M * 32 + 1;
+    hipError_t e = c.ensure(nd * 8 + 16 + (size_t)n_wp, 0, 0);
+    if (e != hipSuccess) return buffers_error(e);
+    double* h_wp = c.h_in.as<double>();
+    double* h_val = h_wp + 3 * n_wp;
+    double* h_Tin = h_val + (size_t)12 * n_wp;
+    double* h_T = h_Tin + M;
+    double* h_C = h_T + M;
+    double* h_t0 = h_C + (size_t)M * 30;
+    int32_t* h_off = reinterpret_cast<int32_t*>(h_t0 + 1);
+    int32_t* h_st = h_off + 2;
+    uint8_t* h_mask = reinterpret_cast<uint8_t*>(h_off + 4);
+    std::memcpy(h_wp, wp, (size_t)n_wp * 24);
+    std::memcpy(h_val, fixed_val, (size_t)n_wp * 96);
+    std::memcpy(h_mask, fixed_mask, (size_t)n_wp);
+    if (times) std::memcpy(h_Tin, times, (size_t)M * 8);
+    *h_t0 = t0;
+    h_off[0] = 0;
+    h_off[1] = n_wp;
+    h_st[0] = -100;
+    if ((rc = launch_minsnap_constrained_track(h_wp, h_off, M, v_max, a_max, times ? h_Tin : nullptr, h_mask, h_val,
+                                               h_T, h_C, h_st, c.s, "generateTrajectory")))
+        return rc;
+    e = hipStreamSynchronize(c.s);
+    if (e != hipSuccess) {
+        set_error(std::string("generateTrajectory: ") + hipGetErrorString(e));
+        return EPP_ERR_HIP;
+    }
+    if (h_st[0] == -4) {
+        set_error("generateTrajectory: a constraint mask has a bit above bit 3, or a fixed value is not finite");
+        return EPP_ERR_INVALID_ARGUMENT;
+    }
+    if (h_st[0] != 0) {
+        set_error(fit_status_message(h_st[0]));
+        return EPP_ERR_RUNTIME;
+    }
+    int64_t R = 0;
+    if (dt > 0) {  // Trajectory::evaluateRange's recurrence on the fit's times (exact count)
+        RangeIter it;
+        it.init(h_T, M);
+        R = range_count(it, dt);
+    }
+    double* rows = (double*)std::malloc((size_t)std::max<int64_t>(R, 1) * 80);
+    if (!rows) {
+        set_error("generateTrajectory: out of host memory");
+        return EPP_ERR_RUNTIME;
+    }
+    if (R) {
+        rc = EPP_OK;
+        if ((e = c.ensure(0, (size_t)R * 80, 0)) != hipSuccess) rc = buffers_error(e);
+        if (!rc)
+            rc = launch_sample_rows_track(h_T, h_C, h_off, M, dt, h_t0, c.h_out.as<double>(), R, c.s,
+                                          "generateTrajectory");
+        if (!rc && (e = hipStreamSynchronize(c.s)) != hipSuccess) {
+            set_error(std::string("generateTrajectory: ") + hipGetErrorString(e));
+            rc = EPP_ERR_HIP;
+        }
+        if (rc) {
+            std::free(rows);
+            return rc;
+        }
+        std::memcpy(rows, c.h_out.p, (size_t)R * 80);
+    }
+    *rows_out = rows;
+    *n_rows = R;
+    return EPP_OK;
+}
+
 }  // namespace
 }  // namespace epp
 
@@ -218,6 +314,13 @@ epp_status epp_generate_trajectory_times_host(const double* wp, int32_t n_wp, co
         return EPP_ERR_INVALID_ARGUMENT;
     }
     return generate_trajectory(wp, n_wp, seg_times, 0.0, 0.0, dt, t0, v0, a0, rows_out, n_rows);
+}
+
+epp_status epp_generate_trajectory_constrained_host(const double* wp, int32_t n_wp, double v_max, double a_max,
+                                                    const double* seg_times, double dt, double t0,
+                                                    const uint8_t* fixed_mask, const double* fixed_val,
+                                                    double** rows_out, int64_t* n_rows) {
+    return generate_constrained(wp, n_wp, v_max, a_max, seg_times, dt, t0, fixed_mask, fixed_val, rows_out, n_rows);
 }
 
 epp_status epp_generate_trajectory_limited_host(const double* wp, int32_t n_wp, double v_max, double a_max, double dt,

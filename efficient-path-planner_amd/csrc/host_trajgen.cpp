@@ -71,4 +71,30 @@ bool generateTrajectoryWithinLimits(const std::vector<epp::Vec3>& waypoints, dou
     return true;
 }
 
+bool generateTrajectoryConstrained(const std::vector<epp::Vec3>& waypoints, double v_max, double a_max,
+                                   double sampling_intervall, double startTimeOffset, const epp::WaypointPins& pins,
+                                   epp::Matrix& result) {
+    if (waypoints.size() < 2) throw std::invalid_argument("At least two waypoints are required");
+    if (pins.mask.size() != waypoints.size() || pins.values.size() != waypoints.size() * 12)
+        throw std::invalid_argument("generateTrajectoryConstrained: pins need one mask byte and 12 values per waypoint");
+    std::vector<double> wp(waypoints.size() * 3);
+    for (size_t i = 0; i < waypoints.size(); ++i) {
+        wp[3 * i] = waypoints[i].x;
+        wp[3 * i + 1] = waypoints[i].y;
+        wp[3 * i + 2] = waypoints[i].z;
+    }
+    double* rows = nullptr;
+    int64_t n = 0;
+    const epp_status rc = epp_generate_trajectory_constrained_host(
+        wp.data(), (int32_t)waypoints.size(), v_max, a_max, nullptr, sampling_intervall, startTimeOffset,
+        pins.mask.data(), pins.values.data(), &rows, &n);
+    if (rc == EPP_ERR_INVALID_ARGUMENT) throw std::invalid_argument(epp_last_error());
+    if (rc != EPP_OK) throw std::runtime_error(std::string("generateTrajectory: ") + epp_last_error());
+    result.rows = (size_t)n;
+    result.cols = 10;
+    result.data.assign(rows, rows + (size_t)n * 10);
+    epp_host_free(rows);
+    return true;
+}
+
 }  // namespace poly_traj

@@ -204,6 +204,9 @@ epp_status minsnap_batch(const double* wp, const int32_t* wp_offsets, int32_t n_
 
 }  // namespace
 
+// The batch fits' segment scratch of a device (minsnap_constrained.hip shares it).
+CachedWs& minsnap_workspace(int dev) { return g_minsnap_ws[dev & 63]; }
+
 // The track offsets of a batch (they live on the device; the launchers need the largest
 // segment count to size LDS and the total for the global scratch; minsnap_kernels.h).
 epp_status read_offsets(const int32_t* d_off, int n_tracks, hipStream_t s, const char* what, int* max_m,

@@ -7,6 +7,8 @@
 //   minsnap_solve.h     the solve of one track by one workgroup (solve_track) and its constants
 //   minsnap.hip         the batch stage: k_minsnap, k_sample_count, k_sample_rows behind
 //                       epp_minsnap_batch[_times], epp_sample_count, epp_sample_batch
+//   minsnap_constrained.hip  the batch fit with the caller's constraints: k_minsnap_constrained
+//                       behind epp_minsnap_batch_constrained
 //   minsnap_refit.hip   the 50 Hz latency path: one track fitted and sampled in one launch
 //                       (k_refit, k_check_refit) behind generate_trajectory_into /
 //                       check_and_generate_into (epp_internal.h)
@@ -31,6 +33,19 @@ namespace epp {
 epp_status launch_minsnap_track(const double* wp, const int32_t* wp_off, int M, double v_max, double a_max,
                                 const double* v0, const double* a0, double* seg_times, double* coeffs,
                                 int32_t* status, hipStream_t st, const char* what);
+
+// (minsnap_constrained.hip) k_minsnap_constrained over one track of M segments: as
+// epp_minsnap_batch_constrained (times_in NULL: Nfabian times; fixed_mask M + 1 bytes, fixed_val
+// (M + 1) x 12)
+epp_status launch_minsnap_constrained_track(const double* wp, const int32_t* wp_off, int M, double v_max, double a_max,
+                                            const double* times_in, const uint8_t* fixed_mask,
+                                            const double* fixed_val, double* seg_times, double* coeffs,
+                                            int32_t* status, hipStream_t st, const char* what);
+
+// (minsnap.hip) the per-device workspace that holds the segment scratch of long tracks for
+// both batch fits (k_minsnap, k_minsnap_constrained)
+struct CachedWs;
+CachedWs& minsnap_workspace(int dev);
 
 // (minsnap.hip) k_sample_rows over the same track: at most cap_rows rows (the host's count of
 // the recurrence) to rows, the time column offset by *t0

@@ -137,18 +137,42 @@ __host__ __device__ constexpr size_t vertex_doubles(int M) { return (size_t)(M +
 // Tracks with up to this many segments keep the segment scratch in LDS (~114 KB at 40).
 constexpr int kMaxLdsSeg = 40;
 
+// The constraint policy of solve_track: which derivatives of which vertices are prescribed
+// besides the positions (the reference's Vertex::addConstraint, src/vertex.cpp:30-60).
+//   NoPins        generateTrajectory's set: the start vertex {v0, a0, 0, 0}, the end vertex at
+//                 rest, derivatives 1..4 of every inner vertex free.  solve_track compiles to
+//                 the code it was before the policy existed.
+//   VertexPins    (minsnap_constrained.hip) the caller's: all four derivatives of the two end
+//                 vertices, and any subset of an inner vertex's.  mask: one byte per vertex
+//                 (LDS), bit k-1 = derivative k is fixed, 0xF at the two ends; val: 12 doubles
+//                 per vertex, (k-1) * 3 + d, read only where the bit is set.
+// A fixed derivative of an inner vertex stays inside the 4 x 4 block system as a unit row and
+// column (build_blocks) whose right-hand side is the value; the rows it coupled to take
+// -R[row][fixed] * value into theirs (rhs_entry), as they do for the end vertices' values.
+struct NoPins {
+    static constexpr bool kOn = false;
+};
+struct VertexPins {
+    static constexpr bool kOn = true;
+    const uint8_t* mask;
+    const double* val;
+    __device__ __forceinline__ bool fixed(int v, int k) const { return (mask[v] >> (k - 1)) & 1; }
+    __device__ __forceinline__ double value(int v, int k, int d) const { return val[((size_t)v * 4 + (k - 1)) * 3 + d]; }
+};
+
 // The min-snap solve of one track by one workgroup of BLOCK threads (every thread calls
 // it; it contains barriers).  kc: the constants (LDS).  P: W x 3 waypoints; v0/a0: the start vertex's velocity and
 // acceleration (NULL = 0); times_in: caller segment times (NULL = Nfabian).  scr: M x
-// Seg::kSize, dv/rhs/Tm/xch: vertex_doubles(M) (LDS).  *s_err must be 0 and
-// visible to every thread on entry.  Writes T_out (M, may be NULL) and C_out (M x 3 x 10,
-// increasing powers).  Returns 0, -2 (a segment time <= 0: the reference's
+// Seg::kSize, dv/rhs/Tm/xch: vertex_doubles(M) (LDS).  pins: the constraint policy (with
+// VertexPins v0 / a0 are not read).  *s_err must be 0 and visible to every thread on entry.
+// Writes T_out (M, may be NULL) and C_out (M x 3 x 10, increasing powers).  Returns 0, -2 (a segment time <= 0: the reference's
 // CHECK_GT(segment_time, 0), impl :297) or -3 (R_pp not SPD).
-template <int BLOCK, bool SCR_LDS>
+template <int BLOCK, bool SCR_LDS, class PINS = NoPins>
 __device__ __forceinline__ int solve_track(const double* __restrict__ kc, const double* __restrict__ P, int M, double vmax, double amax,
                                            const double* v0, const double* a0, const double* times_in,
                                            double* scr, double* dv, double* rhs, double* Tm, double* xch,
-                                           int* s_err, double* T_out, double* C_out, bool refine) {
+                                           int* s_err, double* T_out, double* C_out, bool refine,
+                                           const PINS& pins = PINS()) {
     const int tid = threadIdx.x;
     // ---- phase 1: segment times, powers of T, fixed vertex values ---------------
     // (one barrier: every thread of a segment's powers takes its time itself -- the
@@ -176,6 +200,7 @@ __device__ __forceinline__ int solve_track(const double* __restrict__ kc, const 
         const int v = e / 15, k = (e % 15) / 3, d = e % 3;
         double val = 0.0;  // free values are overwritten by the solve
         if (k == 0) val = P[3 * v + d];
+        else if constexpr (PINS::kOn) val = pins.fixed(v, k) ? pins.value(v, k, d) : 0.0;  // (a free slot may hold NaN)
         else if (v == 0 && k == 1) val = v0 ? v0[d] : 0.0;
         else if (v == 0 && k == 2) val = a0 ? a0[d] : 0.0;
         dv[e] = val;
@@ -193,6 +218,16 @@ __device__ __forceinline__ int solve_track(const double* __restrict__ kc, const 
             const int v = 1 + e / 16, p = (e % 16) / 4, q = e % 4;
             const double* pm = scr + (size_t)(v - 1) * Seg::kSize + Seg::kPow;
             const double* pp = scr + (size_t)v * Seg::kSize + Seg::kPow;
+            if constexpr (PINS::kOn) {
+                // a fixed (v, p+1): unit row and column of D_v, zero row of E_v; a fixed
+                // (v+1, q+1): zero column of E_v
+                const bool fd = pins.fixed(v, p + 1) | pins.fixed(v, q + 1);
+                const bool fe = v >= nin || (pins.fixed(v, p + 1) | pins.fixed(v + 1, q + 1));
+                scr[(size_t)(v - 1) * Seg::kSize + Seg::kL + p * 4 + q] =
+                    fd ? (p == q ? 1.0 : 0.0) : hess(kc, pm, 6 + p, 6 + q) + hess(kc, pp, 1 + p, 1 + q);
+                scr[(size_t)(v - 1) * Seg::kSize + Seg::kW + p * 4 + q] = fe ? 0.0 : hess(kc, pp, 1 + p, 6 + q);
+                continue;
+            }
             scr[(size_t)(v - 1) * Seg::kSize + Seg::kL + p * 4 + q] = hess(kc, pm, 6 + p, 6 + q) + hess(kc, pp, 1 + p, 1 + q);
             scr[(size_t)(v - 1) * Seg::kSize + Seg::kW + p * 4 + q] = (v < nin) ? hess(kc, pp, 1 + p, 6 + q) : 0.0;
         }
@@ -202,7 +237,16 @@ __device__ __forceinline__ int solve_track(const double* __restrict__ kc, const 
     // polynomial without changing its snap), so H[r][0] p_a + H[r][5] p_b = H[r][0] (p_a - p_b)
     // -- the same value without the cancellation of two large terms when the positions are
     // large next to their difference (hess(., 5) := -hess(., 0)).
+    // (VertexPins: "fixed" is the mask's word, the two end vertices included; the row of a
+    // fixed (v, p+1) is the unit row, its entry the value itself, which dv holds)
+    auto is_fixed = [&](int vv, int k) -> bool {
+        if constexpr (PINS::kOn) return pins.fixed(vv, k);
+        else return vv == 0 || vv == M;
+    };
     auto rhs_entry = [&](int v, int p, int d) -> double {
+        if constexpr (PINS::kOn) {
+            if (pins.fixed(v, p + 1)) return dv[(v * HALF + 1 + p) * 3 + d];
+        }
         double s = 0.0;
         // segment v-1: rows 0..4 = vertex v-1, rows 5..9 = vertex v; row of (v,p+1) = 6+p
         {
@@ -210,7 +254,7 @@ __device__ __forceinline__ int solve_track(const double* __restrict__ kc, const 
             s = hess(kc, pw, 6 + p, 0) * (dv[((v - 1) * HALF) * 3 + d] - dv[(v * HALF) * 3 + d]);
             for (int r = 1; r < N; ++r) {
                 const int vv = (r < HALF) ? v - 1 : v, k = r % HALF;
-                if (k != 0 && (vv == 0 || vv == M)) s = s + hess(kc, pw, 6 + p, r) * dv[(vv * HALF + k) * 3 + d];
+                if (k != 0 && is_fixed(vv, k)) s = s + hess(kc, pw, 6 + p, r) * dv[(vv * HALF + k) * 3 + d];
             }
         }
         // segment v: rows 0..4 = vertex v (row of (v,p+1) = 1+p), rows 5..9 = vertex v+1
@@ -219,7 +263,7 @@ __device__ __forceinline__ int solve_track(const double* __restrict__ kc, const 
             s = s + hess(kc, pw, 1 + p, 0) * (dv[(v * HALF) * 3 + d] - dv[((v + 1) * HALF) * 3 + d]);
             for (int r = 1; r < N; ++r) {
                 const int vv = (r < HALF) ? v : v + 1, k = r % HALF;
-                if (k != 0 && (vv == 0 || vv == M)) s = s + hess(kc, pw, 1 + p, r) * dv[(vv * HALF + k) * 3 + d];
+                if (k != 0 && is_fixed(vv, k)) s = s + hess(kc, pw, 1 + p, r) * dv[(vv * HALF + k) * 3 + d];
             }
         }
         return -s;
@@ -360,7 +404,13 @@ __device__ __forceinline__ int solve_track(const double* __restrict__ kc, const 
             if (grp == 0 && act && !mat) {  // x_m = (middle block)^-1 (middle rhs)
                 const double x = tr * id;
                 rhs[(size_t)m * 12 + (L - 16)] = x;
-                dv[((size_t)m * HALF + 1) * 3 + (L - 16)] = x;  // derivatives 1..4 of vertex m
+                // derivatives 1..4 of vertex m (a fixed one keeps its given value in dv, not
+                // the unit row's answer, which is the value to rounding)
+                if constexpr (PINS::kOn) {
+                    if (!pins.fixed(m, row + 1)) dv[((size_t)m * HALF + 1) * 3 + (L - 16)] = x;
+                } else {
+                    dv[((size_t)m * HALF + 1) * 3 + (L - 16)] = x;
+                }
                 xch[96 + (L - 16)] = x;
                 xch[96 + 24 + (L - 16)] = x;
             }
@@ -396,7 +446,12 @@ __device__ __forceinline__ int solve_track(const double* __restrict__ kc, const 
                 const double x = gx - (fma(Gr[0], xn[d], Gr[1] * xn[3 + d]) + fma(Gr[2], xn[6 + d], Gr[3] * xn[9 + d]));
                 if (live && L < 12) {
                     xb[(buf ^ 1) * 12 + L] = x;
-                    dv[((size_t)v * HALF + 1) * 3 + L] = x;  // derivatives 1..4 of vertex v
+                    // derivatives 1..4 of vertex v
+                    if constexpr (PINS::kOn) {
+                        if (!pins.fixed(v, p + 1)) dv[((size_t)v * HALF + 1) * 3 + L] = x;
+                    } else {
+                        dv[((size_t)v * HALF + 1) * 3 + L] = x;
+                    }
                 }
 #pragma unroll
                 for (int k = 0; k < 4; ++k) Gr[k] = Gn[k];
@@ -425,6 +480,24 @@ __device__ __forceinline__ int solve_track(const double* __restrict__ kc, const 
             const double* pm = scr + (size_t)(v - 1) * Seg::kSize + Seg::kPow;  // segment v-1
             const double* pp = scr + (size_t)v * Seg::kSize + Seg::kPow;        // segment v
             double r = rhs_entry(v, p, d);
+            if constexpr (PINS::kOn) {
+                // the masked blocks: a fixed row's residual is value - dv = 0; a free row's
+                // sum leaves the fixed columns out (rhs_entry took them)
+                if (pins.fixed(v, p + 1)) {
+                    r = 0.0;
+                } else {
+                    for (int q = 0; q < 4; ++q) {
+                        if (!pins.fixed(v, q + 1))
+                            r = r - (hess(kc, pm, 6 + p, 6 + q) + hess(kc, pp, 1 + p, 1 + q)) * dv[(v * HALF + 1 + q) * 3 + d];
+                        if (v < nin && !pins.fixed(v + 1, q + 1))
+                            r = r - hess(kc, pp, 1 + p, 6 + q) * dv[((v + 1) * HALF + 1 + q) * 3 + d];
+                        if (v > 1 && !pins.fixed(v - 1, q + 1))
+                            r = r - hess(kc, pm, 1 + q, 6 + p) * dv[((v - 1) * HALF + 1 + q) * 3 + d];
+                    }
+                }
+                rhs[(v * 4 + p) * 3 + d] = r;
+                continue;
+            }
             for (int q = 0; q < 4; ++q) {
                 r = r - (hess(kc, pm, 6 + p, 6 + q) + hess(kc, pp, 1 + p, 1 + q)) * dv[(v * HALF + 1 + q) * 3 + d];
                 if (v < nin) r = r - hess(kc, pp, 1 + p, 6 + q) * dv[((v + 1) * HALF + 1 + q) * 3 + d];
@@ -444,6 +517,9 @@ __device__ __forceinline__ int solve_track(const double* __restrict__ kc, const 
         if (*s_err) return -3;
         for (int e = tid; e < nin * 12; e += BLOCK) {
             const int v = 1 + e / 12, p = (e % 12) / 3, d = e % 3;
+            if constexpr (PINS::kOn) {
+                if (pins.fixed(v, p + 1)) continue;  // (the second solve left the given value in dv, too)
+            }
             double& x = dv[(v * HALF + 1 + p) * 3 + d];
             x = scr[(size_t)(v - 1) * Seg::kSize + Seg::kX + p * 3 + d] + x;
         }

@@ -92,6 +92,9 @@ def lib() -> C.CDLL:
             "epp_check_motions": (i32, [vp, vp, vp, i64, i32, i32, vp, vp]),
             "epp_minsnap_batch": (i32, [vp, vp, i32, dp, dp, vp, vp, vp, vp, vp, vp]),
             "epp_minsnap_batch_times": (i32, [vp, vp, i32, vp, vp, vp, vp, vp, vp]),
+            "epp_minsnap_batch_constrained": (i32, [vp, vp, i32, dp, dp, vp, vp, vp, vp, vp, vp, vp]),
+            "epp_generate_trajectory_constrained_host": (i32, [vp, i32, dp, dp, vp, dp, dp, vp, vp,
+                                                               C.POINTER(C.POINTER(C.c_double)), C.POINTER(i64)]),
             "epp_sample_count": (i32, [vp, vp, i32, dp, vp, vp]),
             "epp_sample_batch": (i32, [vp, vp, vp, i32, dp, vp, vp, vp, vp]),
             "epp_traj_peaks": (i32, [vp, vp, vp, i32, vp, vp, vp]),
@@ -187,7 +190,8 @@ EXPORTED = [
     "epp_sample_derivative_batch", "epp_thrust_rates", "epp_traj_thrust_rates_batch", "epp_device_cu_count",
     "epp_traj_thrust_grid_batch", "epp_traj_scale_to_thrust_limits", "epp_generate_trajectory_flyable_host",
     "epp_traj_snap_cost", "epp_minsnap_time_gradient", "epp_minsnap_optimize_times",
-    "epp_generate_trajectory_timeopt_host",
+    "epp_generate_trajectory_timeopt_host", "epp_minsnap_batch_constrained",
+    "epp_generate_trajectory_constrained_host",
 ]
 
 
@@ -507,6 +511,78 @@ def minsnap_batch_times(tracks, times, v0=None, a0=None):
     return [Cf[int(off[k]) - k:int(off[k + 1]) - k - 1] for k in range(nt)], st
 
 
+def minsnap_batch_constrained(tracks, v_max, a_max, masks, values, times=None):
+    """epp_minsnap_batch_constrained on a list of (W_k x 3) waypoint arrays: masks a list of
+    uint8[W_k] (bit k-1: derivative k is fixed at the waypoint; ignored at a track's two ends,
+    where all four are), values a list of float64[W_k, 4, 3] (derivative k at [w, k-1]; slots
+    whose bit is clear at inner waypoints are not read), times a list of (W_k - 1) segment
+    times or None (Nfabian times under v_max / a_max, which ignore the fixed values).
+
+    Returns (seg_times list, coeffs list [M_k x 3 x 10], status array) like minsnap_batch."""
+    nt = len(tracks)
+    if nt == 0:
+        check(lib().epp_minsnap_batch_constrained(None, None, 0, float(v_max), float(a_max), None, None, None,
+                                                  None, None, None, None))
+        return [], [], np.zeros(0, np.int32)
+    wp = np.ascontiguousarray(np.concatenate([np.asarray(t, np.float64).reshape(-1, 3) for t in tracks]))
+    off = np.zeros(nt + 1, np.int32)
+    off[1:] = np.cumsum([len(t) for t in tracks])
+    nw = int(off[-1])
+    nseg = nw - nt
+    mask = np.ascontiguousarray(np.concatenate([np.asarray(m, np.uint8).ravel() for m in masks]))
+    val = np.ascontiguousarray(np.concatenate([np.asarray(v, np.float64).reshape(-1, 12) for v in values]))
+    if len(mask) != nw or len(val) != nw:
+        raise ValueError("minsnap_batch_constrained: masks and values need one entry per waypoint")
+    d_wp, d_off = DeviceBuffer.from_array(wp), DeviceBuffer.from_array(off)
+    d_mask, d_val = DeviceBuffer.from_array(mask), DeviceBuffer.from_array(val)
+    d_Tin = None
+    if times is not None:
+        Tin = np.ascontiguousarray(np.concatenate([np.asarray(t, np.float64).ravel() for t in times] + [np.zeros(0)]))
+        if len(Tin) != nseg:
+            raise ValueError("minsnap_batch_constrained: times needs one entry per segment")
+        d_Tin = DeviceBuffer.from_array(Tin) if nseg else DeviceBuffer(8)
+    d_T, d_C, d_st = DeviceBuffer(8 * max(nseg, 1)), DeviceBuffer(240 * max(nseg, 1)), DeviceBuffer(4 * nt)
+    d_T.zero()
+    d_C.zero()
+    check(lib().epp_minsnap_batch_constrained(d_wp.ptr, d_off.ptr, nt, float(v_max), float(a_max),
+                                              d_Tin.ptr if d_Tin else None, d_mask.ptr, d_val.ptr, d_T.ptr, d_C.ptr,
+                                              d_st.ptr, None))
+    sync()
+    T = d_T.download(np.float64, nseg)
+    Cf = d_C.download(np.float64, nseg * 30).reshape(nseg, 3, 10)
+    st = d_st.download(np.int32, nt)
+    Ts, Cs = [], []
+    for k in range(nt):
+        a, b = int(off[k]) - k, int(off[k + 1]) - k - 1
+        Ts.append(T[a:max(a, b)])
+        Cs.append(Cf[a:max(a, b)])
+    return Ts, Cs, st
+
+
+def generate_trajectory_constrained(waypoints, v_max, a_max, dt, mask, values, seg_times=None, t0=0.0) -> np.ndarray:
+    """generateTrajectory under the caller's constraints (epp_generate_trajectory_constrained_host):
+    mask uint8[W], values float64[W, 4, 3] as in minsnap_batch_constrained; seg_times None: Nfabian."""
+    wp = np.ascontiguousarray(np.asarray(waypoints, np.float64).reshape(-1, 3))
+    mask = np.ascontiguousarray(np.asarray(mask, np.uint8).ravel())
+    val = np.ascontiguousarray(np.asarray(values, np.float64).reshape(-1, 12))
+    if len(mask) != len(wp) or len(val) != len(wp):
+        raise ValueError("generate_trajectory_constrained: mask and values need one entry per waypoint")
+    T = None if seg_times is None else np.ascontiguousarray(seg_times, np.float64)
+    if T is not None and len(T) != len(wp) - 1:
+        raise ValueError("generate_trajectory_constrained: seg_times needs one entry per segment")
+    rows = C.POINTER(C.c_double)()
+    n = C.c_int64(0)
+    check(lib().epp_generate_trajectory_constrained_host(_ptr(wp), len(wp), float(v_max), float(a_max),
+                                                         _ptr(T) if T is not None else None, float(dt), float(t0),
+                                                         _ptr(mask), _ptr(val), C.byref(rows), C.byref(n)))
+    if n.value == 0:
+        lib().epp_host_free(C.cast(rows, C.c_void_p))
+        return np.zeros((0, 10))
+    out = np.ctypeslib.as_array(rows, shape=(n.value * 10,)).copy().reshape(-1, 10)
+    lib().epp_host_free(C.cast(rows, C.c_void_p))
+    return out
+
+
 def generate_trajectory_times(waypoints, seg_times, dt, t0=0.0, v0=(0, 0, 0), a0=(0, 0, 0)) -> np.ndarray:
     """generateTrajectory with the caller's segment times (epp_generate_trajectory_times_host)."""
     wp = np.ascontiguousarray(np.asarray(waypoints, np.float64).reshape(-1, 3))
@@ -635,6 +711,38 @@ def gate_frames(centres, yaws) -> np.ndarray:
     yaws = np.asarray(yaws, np.float64).reshape(-1)
     assert len(yaws) == len(centres)
     return np.ascontiguousarray(np.column_stack([centres, np.cos(yaws), np.sin(yaws)]))
+
+
+def gate_velocity_pins(frames, waypoints, gate_rows, speed: float):
+    """The constraints that send one track through its gates along their normals: for every
+    inner waypoint w with gate_rows[w] = g >= 0 (the row of the frame table whose centre the
+    waypoint sits at; -1: no gate), derivative 1 is fixed to speed times gate g's normal.  The
+    normal is the gate frame's y axis, (sin(yaw), cos(yaw), 0) in the world (gate_pass.h: a
+    crossing goes from negative to positive gate-frame y), with the sign that gives it a
+    non-negative dot product with (next waypoint - previous waypoint).  The first and the last
+    waypoint are left alone: their states are the caller's.  Host code only.
+
+    Returns (mask uint8[W], values float64[W, 4, 3]) for minsnap_batch_constrained, the two end
+    rows of values zero."""
+    frames = np.asarray(frames, np.float64).reshape(-1, 5)
+    wp = np.asarray(waypoints, np.float64).reshape(-1, 3)
+    rows = np.asarray(gate_rows, np.int64).reshape(-1)
+    if len(rows) != len(wp):
+        raise ValueError("gate_velocity_pins: gate_rows needs one entry per waypoint")
+    if (rows >= len(frames)).any():
+        raise ValueError("gate_velocity_pins: a gate row is outside the frame table")
+    mask = np.zeros(len(wp), np.uint8)
+    values = np.zeros((len(wp), 4, 3))
+    for w in range(1, len(wp) - 1):
+        g = int(rows[w])
+        if g < 0:
+            continue
+        n = np.array([frames[g, 4], frames[g, 3], 0.0])
+        if np.dot(n, wp[w + 1] - wp[w - 1]) < 0.0:
+            n = -n
+        mask[w] |= 1
+        values[w, 0] = float(speed) * n
+    return mask, values
 
 
 def gates_crossed(frames, half_edge: float, s1: np.ndarray, s2: np.ndarray) -> np.ndarray:

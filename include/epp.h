@@ -212,6 +212,30 @@ epp_status epp_minsnap_batch(const double* wp, const int32_t* wp_offsets, int32_
 epp_status epp_minsnap_batch_times(const double* wp, const int32_t* wp_offsets, int32_t n_tracks, const double* v0,
                                    const double* a0, const double* seg_times_in, double* coeffs, int32_t* status,
                                    void* stream);
+/* As epp_minsnap_batch with the caller's constraints on the vertices instead of
+ * generateTrajectory's fixed set: what the reference's library takes through
+ * Vertex::addConstraint (external/poly_traj/src/vertex.cpp:30-60) and its generateTrajectory
+ * never uses.  Per waypoint w of wp (all device):
+ *   fixed_mask[w]   bit k-1 set: derivative k (1..4: velocity, acceleration, jerk, snap) is
+ *                   fixed at w; a bit above bit 3 gives status -4
+ *   fixed_val       12 doubles, the x, y, z of derivative k at (w*4 + (k-1))*3 + d
+ * At the first and the last waypoint of a track all four derivatives are fixed
+ * (Vertex::makeStartOrEnd, :146-170): the mask there is ignored and the four values are
+ * read.  epp_minsnap_batch's fit is fixed_val = [v0, a0, 0, 0] at the start, zeros at the end
+ * and mask 0 inside.  A slot whose bit is clear at an inner waypoint is never read (it may
+ * hold NaN); a non-finite value in a slot that is used gives status -4.  A fixed derivative
+ * is met exactly (the segments on both sides are built from the given value) and the rest
+ * stay continuous; a waypoint with all four fixed splits the fit there.
+ * seg_times_in (total segments, device; may be seg_times): the caller's segment times as in
+ * epp_minsnap_batch_times, NULL: Nfabian times of the positions under v_max / a_max -- they
+ * ignore the fixed values, as they ignore v0 in epp_minsnap_batch, so a track pinned to
+ * speeds far from v_max wants the caller's times.  Outputs and status 0, -1, -2, -3 as
+ * epp_minsnap_batch; a track with status -4 is left unwritten.
+ * EPP_ERR_INVALID_ARGUMENT for a NULL fixed_mask or fixed_val with n_tracks > 0. */
+epp_status epp_minsnap_batch_constrained(const double* wp, const int32_t* wp_offsets, int32_t n_tracks,
+                                         double v_max, double a_max, const double* seg_times_in,
+                                         const uint8_t* fixed_mask, const double* fixed_val, double* seg_times,
+                                         double* coeffs, int32_t* status, void* stream);
 /* Number of rows Trajectory::evaluateRange produces for every track (device int64 out). */
 epp_status epp_sample_count(const double* seg_times, const int32_t* wp_offsets, int32_t n_tracks,
                             double dt, int64_t* row_counts, void* stream);
@@ -727,6 +751,16 @@ epp_status epp_generate_trajectory_host(const double* wp, int32_t n_wp, double v
 epp_status epp_generate_trajectory_times_host(const double* wp, int32_t n_wp, const double* seg_times, double dt,
                                               double t0, const double v0[3], const double a0[3], double** rows,
                                               int64_t* n_rows);
+/* The same under the caller's constraints (epp_minsnap_batch_constrained above: fixed_mask
+ * n_wp bytes, fixed_val n_wp x 12, HOST arrays here): the constrained fit at seg_times
+ * (n_wp - 1 of them, NULL: Nfabian times under v_max / a_max), then evaluateRange sampling.
+ * Two launches over pinned host buffers; the rows are those of epp_sample_batch on
+ * epp_minsnap_batch_constrained's output.  Errors as epp_generate_trajectory_host; also
+ * EPP_ERR_INVALID_ARGUMENT for a mask bit above bit 3 or a non-finite value in a used slot. */
+epp_status epp_generate_trajectory_constrained_host(const double* wp, int32_t n_wp, double v_max, double a_max,
+                                                    const double* seg_times, double dt, double t0,
+                                                    const uint8_t* fixed_mask, const double* fixed_val,
+                                                    double** rows, int64_t* n_rows);
 /* epp_generate_trajectory_host with v_max and a_max enforced on the fitted trajectory:
  * fit, then Trajectory::scaleSegmentTimesToMeetConstraints (external/poly_traj/src/
  * trajectory.cpp:385-429; epp_traj_scale_to_limits above), then evaluateRange sampling of
