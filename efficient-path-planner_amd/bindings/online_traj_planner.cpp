@@ -6,6 +6,7 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <algorithm>
 #include <cstring>
 #include <stdexcept>
 #include <string>
@@ -41,6 +42,39 @@ static Matrix to_matrix(const py::object& o) {
 static py::array_t<double> from_matrix(const Matrix& m) {
     py::array_t<double> out({(py::ssize_t)m.rows, (py::ssize_t)m.cols});
     if (!m.data.empty()) std::memcpy(out.mutable_data(), m.data.data(), m.data.size() * sizeof(double));
+    return out;
+}
+
+// An (n, 3) array as waypoints.
+static std::vector<Vec3> read_waypoints(const py::object& o) {
+    const Matrix w = to_matrix(o);
+    if (w.cols != 3) throw std::invalid_argument("waypoints must be an (n, 3) array");
+    std::vector<Vec3> wp;
+    for (size_t i = 0; i < w.rows; ++i) wp.emplace_back(w(i, 0), w(i, 1), w(i, 2));
+    return wp;
+}
+
+static std::vector<std::vector<Vec3>> read_waypoint_sets(const std::vector<py::object>& waypointSets) {
+    std::vector<std::vector<Vec3>> sets;
+    for (const auto& o : waypointSets) sets.push_back(read_waypoints(o));
+    return sets;
+}
+
+// The values of v as an array of T: one-dimensional, or of the given shape (v.size() elements).
+template <class T, class U>
+static py::array_t<T> to_array(const std::vector<U>& v, std::vector<py::ssize_t> shape = {}) {
+    if (shape.empty()) shape.push_back((py::ssize_t)v.size());
+    py::array_t<T> a(shape);
+    if ((size_t)a.size() != v.size()) throw std::runtime_error("to_array: the shape does not hold the values");
+    std::copy(v.begin(), v.end(), a.mutable_data());
+    return a;
+}
+
+// Points as an (n, 3) array.
+static py::array_t<double> from_points(const std::vector<Vec3>& pts) {
+    py::array_t<double> out({(py::ssize_t)pts.size(), (py::ssize_t)3});
+    for (size_t i = 0; i < pts.size(); ++i)
+        for (int k = 0; k < 3; ++k) out.mutable_data()[i * 3 + k] = pts[i][k];
     return out;
 }
 
@@ -87,10 +121,7 @@ PYBIND11_MODULE(online_traj_planner, m) {
                     ok = self.planPath(s, g, timeLimit, path);
                 }
                 if (!ok) return py::none();
-                py::array_t<double> out({(py::ssize_t)path.size(), (py::ssize_t)3});
-                for (size_t i = 0; i < path.size(); ++i)
-                    for (int k = 0; k < 3; ++k) out.mutable_data()[i * 3 + k] = path[i][k];
-                return out;
+                return from_points(path);
             },
             py::arg("start"), py::arg("goal"), py::arg("timeLimit") = 1.0)
         .def(
@@ -111,10 +142,7 @@ PYBIND11_MODULE(online_traj_planner, m) {
                     py::gil_scoped_release release;
                     flat = self.includeGates2(wp);
                 }
-                py::array_t<double> out({(py::ssize_t)flat.size(), (py::ssize_t)3});
-                for (size_t i = 0; i < flat.size(); ++i)
-                    for (int k = 0; k < 3; ++k) out.mutable_data()[i * 3 + k] = flat[i][k];
-                return out;
+                return from_points(flat);
             },
             py::arg("waypoints"))
         .def(
@@ -130,10 +158,8 @@ PYBIND11_MODULE(online_traj_planner, m) {
             [](const epp::PathPlanner& self, const py::object& traj, double minDistance, const py::object& waypoints,
                double vMax, double aMax, double samplingInterval, double startTimeOffset, const py::object& v0,
                const py::object& a0) {
-                Matrix m = to_matrix(traj), w = to_matrix(waypoints);
-                if (w.cols != 3) throw std::invalid_argument("waypoints must be an (n, 3) array");
-                std::vector<Vec3> wp;
-                for (size_t i = 0; i < w.rows; ++i) wp.emplace_back(w(i, 0), w(i, 1), w(i, 2));
+                const Matrix m = to_matrix(traj);
+                const std::vector<Vec3> wp = read_waypoints(waypoints);
                 const Vec3 v = to_vec3(v0), a = to_vec3(a0);
                 Matrix out;
                 bool valid;
@@ -151,27 +177,14 @@ PYBIND11_MODULE(online_traj_planner, m) {
             "check_candidate_trajectories",  // fit + first collision of K waypoint sets (this build)
             [](const epp::PathPlanner& self, const std::vector<py::object>& waypointSets, double vMax, double aMax,
                double samplingInterval, double minDistance) {
-                std::vector<std::vector<Vec3>> sets;
-                for (const auto& o : waypointSets) {
-                    Matrix w = to_matrix(o);
-                    if (w.cols != 3) throw std::invalid_argument("waypoints must be an (n, 3) array");
-                    std::vector<Vec3> wp;
-                    for (size_t i = 0; i < w.rows; ++i) wp.emplace_back(w(i, 0), w(i, 1), w(i, 2));
-                    sets.push_back(std::move(wp));
-                }
+                const std::vector<std::vector<Vec3>> sets = read_waypoint_sets(waypointSets);
                 std::vector<long> rows;
                 std::vector<double> times;
                 {
                     py::gil_scoped_release release;
                     self.checkCandidateTrajectories(sets, vMax, aMax, samplingInterval, minDistance, rows, &times);
                 }
-                py::array_t<int64_t> r((py::ssize_t)rows.size());
-                py::array_t<double> t((py::ssize_t)times.size());
-                for (size_t i = 0; i < rows.size(); ++i) {
-                    r.mutable_data()[i] = rows[i];
-                    t.mutable_data()[i] = times[i];
-                }
-                return py::make_tuple(r, t);
+                return py::make_tuple(to_array<int64_t>(rows), to_array<double>(times));
             },
             py::arg("waypoint_sets"), py::arg("v_max"), py::arg("a_max"), py::arg("sampling_interval"),
             py::arg("min_distance"))
@@ -179,14 +192,7 @@ PYBIND11_MODULE(online_traj_planner, m) {
             "sweep_candidate_trajectories",  // the same plus the chords between the rows (this build)
             [](const epp::PathPlanner& self, const std::vector<py::object>& waypointSets, double vMax, double aMax,
                double samplingInterval, double minDistance, bool canPassGate) {
-                std::vector<std::vector<Vec3>> sets;
-                for (const auto& o : waypointSets) {
-                    Matrix w = to_matrix(o);
-                    if (w.cols != 3) throw std::invalid_argument("waypoints must be an (n, 3) array");
-                    std::vector<Vec3> wp;
-                    for (size_t i = 0; i < w.rows; ++i) wp.emplace_back(w(i, 0), w(i, 1), w(i, 2));
-                    sets.push_back(std::move(wp));
-                }
+                const std::vector<std::vector<Vec3>> sets = read_waypoint_sets(waypointSets);
                 std::vector<long> rows, chords;
                 std::vector<double> times;
                 {
@@ -194,14 +200,7 @@ PYBIND11_MODULE(online_traj_planner, m) {
                     self.sweepCandidateTrajectories(sets, vMax, aMax, samplingInterval, minDistance, canPassGate, rows,
                                                     chords, &times);
                 }
-                py::array_t<int64_t> r((py::ssize_t)rows.size()), c((py::ssize_t)chords.size());
-                py::array_t<double> t((py::ssize_t)times.size());
-                for (size_t i = 0; i < rows.size(); ++i) {
-                    r.mutable_data()[i] = rows[i];
-                    c.mutable_data()[i] = chords[i];
-                    t.mutable_data()[i] = times[i];
-                }
-                return py::make_tuple(r, c, t);
+                return py::make_tuple(to_array<int64_t>(rows), to_array<int64_t>(chords), to_array<double>(times));
             },
             py::arg("waypoint_sets"), py::arg("v_max"), py::arg("a_max"), py::arg("sampling_interval"),
             py::arg("min_distance"), py::arg("can_pass_gate") = false)
@@ -209,14 +208,7 @@ PYBIND11_MODULE(online_traj_planner, m) {
             "candidate_clearances",  // fit + closest approach of K waypoint sets (this build)
             [](const epp::PathPlanner& self, const std::vector<py::object>& waypointSets, double vMax, double aMax,
                double samplingInterval) {
-                std::vector<std::vector<Vec3>> sets;
-                for (const auto& o : waypointSets) {
-                    Matrix w = to_matrix(o);
-                    if (w.cols != 3) throw std::invalid_argument("waypoints must be an (n, 3) array");
-                    std::vector<Vec3> wp;
-                    for (size_t i = 0; i < w.rows; ++i) wp.emplace_back(w(i, 0), w(i, 1), w(i, 2));
-                    sets.push_back(std::move(wp));
-                }
+                const std::vector<std::vector<Vec3>> sets = read_waypoint_sets(waypointSets);
                 std::vector<double> clearance, times;
                 std::vector<long> rows;
                 std::vector<int> nearest;
@@ -224,16 +216,8 @@ PYBIND11_MODULE(online_traj_planner, m) {
                     py::gil_scoped_release release;
                     self.candidateClearances(sets, vMax, aMax, samplingInterval, clearance, &rows, &times, &nearest);
                 }
-                py::array_t<double> c((py::ssize_t)clearance.size()), t((py::ssize_t)times.size());
-                py::array_t<int64_t> r((py::ssize_t)rows.size());
-                py::array_t<int32_t> o((py::ssize_t)nearest.size());
-                for (size_t i = 0; i < clearance.size(); ++i) {
-                    c.mutable_data()[i] = clearance[i];
-                    r.mutable_data()[i] = rows[i];
-                    t.mutable_data()[i] = times[i];
-                    o.mutable_data()[i] = nearest[i];
-                }
-                return py::make_tuple(c, r, t, o);
+                return py::make_tuple(to_array<double>(clearance), to_array<int64_t>(rows), to_array<double>(times),
+                                      to_array<int32_t>(nearest));
             },
             py::arg("waypoint_sets"), py::arg("v_max"), py::arg("a_max"), py::arg("sampling_interval"))
         .def(
@@ -259,14 +243,7 @@ PYBIND11_MODULE(online_traj_planner, m) {
             "candidate_first_hits",  // fit + first hit of the first failing chord of K waypoint sets (this build)
             [](const epp::PathPlanner& self, const std::vector<py::object>& waypointSets, double vMax, double aMax,
                double samplingInterval, bool canPassGate) {
-                std::vector<std::vector<Vec3>> sets;
-                for (const auto& o : waypointSets) {
-                    Matrix w = to_matrix(o);
-                    if (w.cols != 3) throw std::invalid_argument("waypoints must be an (n, 3) array");
-                    std::vector<Vec3> wp;
-                    for (size_t i = 0; i < w.rows; ++i) wp.emplace_back(w(i, 0), w(i, 1), w(i, 2));
-                    sets.push_back(std::move(wp));
-                }
+                const std::vector<std::vector<Vec3>> sets = read_waypoint_sets(waypointSets);
                 std::vector<double> hits, times;
                 std::vector<long> chords;
                 std::vector<int> obbs;
@@ -274,16 +251,8 @@ PYBIND11_MODULE(online_traj_planner, m) {
                     py::gil_scoped_release release;
                     self.candidateFirstHits(sets, vMax, aMax, samplingInterval, canPassGate, chords, hits, &times, &obbs);
                 }
-                py::array_t<int64_t> c((py::ssize_t)chords.size());
-                py::array_t<double> h((py::ssize_t)hits.size()), t((py::ssize_t)times.size());
-                py::array_t<int32_t> o((py::ssize_t)obbs.size());
-                for (size_t i = 0; i < chords.size(); ++i) {
-                    c.mutable_data()[i] = chords[i];
-                    h.mutable_data()[i] = hits[i];
-                    t.mutable_data()[i] = times[i];
-                    o.mutable_data()[i] = obbs[i];
-                }
-                return py::make_tuple(c, h, t, o);
+                return py::make_tuple(to_array<int64_t>(chords), to_array<double>(hits), to_array<double>(times),
+                                      to_array<int32_t>(obbs));
             },
             py::arg("waypoint_sets"), py::arg("v_max"), py::arg("a_max"), py::arg("sampling_interval"),
             py::arg("can_pass_gate") = false)
@@ -295,14 +264,7 @@ PYBIND11_MODULE(online_traj_planner, m) {
             "candidate_gate_passes",  // fit + ordered gate passage of K waypoint sets (this build)
             [](const epp::PathPlanner& self, const std::vector<py::object>& waypointSets, double vMax, double aMax,
                double samplingInterval, const py::object& frames, double halfEdge) {
-                std::vector<std::vector<Vec3>> sets;
-                for (const auto& o : waypointSets) {
-                    Matrix w = to_matrix(o);
-                    if (w.cols != 3) throw std::invalid_argument("waypoints must be an (n, 3) array");
-                    std::vector<Vec3> wp;
-                    for (size_t i = 0; i < w.rows; ++i) wp.emplace_back(w(i, 0), w(i, 1), w(i, 2));
-                    sets.push_back(std::move(wp));
-                }
+                const std::vector<std::vector<Vec3>> sets = read_waypoint_sets(waypointSets);
                 const Matrix fr = to_matrix(frames);
                 std::vector<long> chords;
                 std::vector<double> times, offsets;
@@ -313,17 +275,8 @@ PYBIND11_MODULE(online_traj_planner, m) {
                                              &offsets);
                 }
                 const py::ssize_t K = (py::ssize_t)sets.size(), G = (py::ssize_t)fr.rows;
-                py::array_t<int64_t> c({K, G});
-                py::array_t<double> t({K, G}), o({K, G, (py::ssize_t)2});
-                py::array_t<int32_t> p(K);
-                for (size_t i = 0; i < chords.size(); ++i) {
-                    c.mutable_data()[i] = chords[i];
-                    t.mutable_data()[i] = times[i];
-                    o.mutable_data()[2 * i] = offsets[2 * i];
-                    o.mutable_data()[2 * i + 1] = offsets[2 * i + 1];
-                }
-                for (size_t i = 0; i < passed.size(); ++i) p.mutable_data()[i] = passed[i];
-                return py::make_tuple(c, t, o, p);
+                return py::make_tuple(to_array<int64_t>(chords, {K, G}), to_array<double>(times, {K, G}),
+                                      to_array<double>(offsets, {K, G, 2}), to_array<int32_t>(passed));
             },
             py::arg("waypoint_sets"), py::arg("v_max"), py::arg("a_max"), py::arg("sampling_interval"),
             py::arg("frames"), py::arg("half_edge") = 0.425)
@@ -331,14 +284,7 @@ PYBIND11_MODULE(online_traj_planner, m) {
             "candidate_thrust_rates",  // fit + thrust / body rate / tilt extremes of K waypoint sets (this build)
             [](const epp::PathPlanner& self, const std::vector<py::object>& waypointSets, double vMax, double aMax,
                double samplingInterval, double g) {
-                std::vector<std::vector<Vec3>> sets;
-                for (const auto& o : waypointSets) {
-                    Matrix w = to_matrix(o);
-                    if (w.cols != 3) throw std::invalid_argument("waypoints must be an (n, 3) array");
-                    std::vector<Vec3> wp;
-                    for (size_t i = 0; i < w.rows; ++i) wp.emplace_back(w(i, 0), w(i, 1), w(i, 2));
-                    sets.push_back(std::move(wp));
-                }
+                const std::vector<std::vector<Vec3>> sets = read_waypoint_sets(waypointSets);
                 std::vector<double> out;
                 std::vector<long> rows;
                 {
@@ -346,11 +292,7 @@ PYBIND11_MODULE(online_traj_planner, m) {
                     self.candidateThrustRates(sets, vMax, aMax, samplingInterval, g, out, &rows);
                 }
                 const py::ssize_t K = (py::ssize_t)sets.size();
-                py::array_t<double> o({K, (py::ssize_t)8});
-                py::array_t<int64_t> r({K, (py::ssize_t)4});
-                for (size_t i = 0; i < out.size(); ++i) o.mutable_data()[i] = out[i];
-                for (size_t i = 0; i < rows.size(); ++i) r.mutable_data()[i] = rows[i];
-                return py::make_tuple(o, r);
+                return py::make_tuple(to_array<double>(out, {K, 8}), to_array<int64_t>(rows, {K, 4}));
             },
             py::arg("waypoint_sets"), py::arg("v_max"), py::arg("a_max"), py::arg("sampling_interval"),
             py::arg("g") = 9.81)
@@ -358,14 +300,7 @@ PYBIND11_MODULE(online_traj_planner, m) {
             "candidate_flyable_scales",  // fit + time scaling to thrust / rate / tilt limits of K waypoint sets (this build)
             [](const epp::PathPlanner& self, const std::vector<py::object>& waypointSets, double vMax, double aMax,
                const std::tuple<double, double, double, double, double>& limits) {
-                std::vector<std::vector<Vec3>> sets;
-                for (const auto& o : waypointSets) {
-                    Matrix w = to_matrix(o);
-                    if (w.cols != 3) throw std::invalid_argument("waypoints must be an (n, 3) array");
-                    std::vector<Vec3> wp;
-                    for (size_t i = 0; i < w.rows; ++i) wp.emplace_back(w(i, 0), w(i, 1), w(i, 2));
-                    sets.push_back(std::move(wp));
-                }
+                const std::vector<std::vector<Vec3>> sets = read_waypoint_sets(waypointSets);
                 const epp::PathPlanner::FlightLimits lim{std::get<0>(limits), std::get<1>(limits), std::get<2>(limits),
                                                          std::get<3>(limits), std::get<4>(limits)};
                 std::vector<double> scale, duration;
@@ -374,45 +309,24 @@ PYBIND11_MODULE(online_traj_planner, m) {
                     py::gil_scoped_release release;
                     self.candidateFlyableScales(sets, vMax, aMax, lim, scale, duration, status, &violated);
                 }
-                const py::ssize_t K = (py::ssize_t)sets.size();
-                py::array_t<double> s(K), d(K);
-                py::array_t<int32_t> st(K), vi(K);
-                for (py::ssize_t i = 0; i < K; ++i) {
-                    s.mutable_data()[i] = scale[i];
-                    d.mutable_data()[i] = duration[i];
-                    st.mutable_data()[i] = status[i];
-                    vi.mutable_data()[i] = violated[i];
-                }
-                return py::make_tuple(s, d, st, vi);
+                return py::make_tuple(to_array<double>(scale), to_array<double>(duration), to_array<int32_t>(status),
+                                      to_array<int32_t>(violated));
             },
             py::arg("waypoint_sets"), py::arg("v_max"), py::arg("a_max"), py::arg("limits"))
         .def(
             "candidate_snap_costs",  // fit (+ descent over the segment times) and snap cost of K waypoint sets (this build)
             [](const epp::PathPlanner& self, const std::vector<py::object>& waypointSets, double vMax, double aMax,
                bool optimize) {
-                std::vector<std::vector<Vec3>> sets;
-                for (const auto& o : waypointSets) {
-                    Matrix w = to_matrix(o);
-                    if (w.cols != 3) throw std::invalid_argument("waypoints must be an (n, 3) array");
-                    std::vector<Vec3> wp;
-                    for (size_t i = 0; i < w.rows; ++i) wp.emplace_back(w(i, 0), w(i, 1), w(i, 2));
-                    sets.push_back(std::move(wp));
-                }
+                const std::vector<std::vector<Vec3>> sets = read_waypoint_sets(waypointSets);
                 std::vector<double> costs;
                 std::vector<std::vector<double>> times;
                 {
                     py::gil_scoped_release release;
                     self.candidateSnapCosts(sets, vMax, aMax, optimize, costs, &times);
                 }
-                py::array_t<double> c((py::ssize_t)costs.size());
-                for (size_t i = 0; i < costs.size(); ++i) c.mutable_data()[i] = costs[i];
                 py::list ts;
-                for (const auto& t : times) {
-                    py::array_t<double> a((py::ssize_t)t.size());
-                    for (size_t i = 0; i < t.size(); ++i) a.mutable_data()[i] = t[i];
-                    ts.append(a);
-                }
-                return py::make_tuple(c, ts);
+                for (const auto& t : times) ts.append(to_array<double>(t));
+                return py::make_tuple(to_array<double>(costs), ts);
             },
             py::arg("waypoint_sets"), py::arg("v_max"), py::arg("a_max"), py::arg("optimize") = false)
         .def(
@@ -466,9 +380,7 @@ PYBIND11_MODULE(online_traj_planner, m) {
                 }
                 py::list out;
                 for (size_t i = 0; i < pr.size(); ++i) {
-                    py::array_t<double> a({(py::ssize_t)paths[i].size(), (py::ssize_t)3});
-                    for (size_t j = 0; j < paths[i].size(); ++j)
-                        for (int k = 0; k < 3; ++k) a.mutable_data()[j * 3 + k] = paths[i][j][k];
+                    py::array_t<double> a = from_points(paths[i]);
                     out.append(py::make_tuple((bool)ok[i], a));
                 }
                 return out;
@@ -490,15 +402,11 @@ PYBIND11_MODULE(online_traj_planner, m) {
                 }
                 py::list segs;
                 for (size_t i = 0; i < pr.size(); ++i) {
-                    py::array_t<double> a({(py::ssize_t)paths[i].size(), (py::ssize_t)3});
-                    for (size_t j = 0; j < paths[i].size(); ++j)
-                        for (int k = 0; k < 3; ++k) a.mutable_data()[j * 3 + k] = paths[i][j][k];
+                    py::array_t<double> a = from_points(paths[i]);
                     segs.append(py::make_tuple((bool)ok[i], a));
                 }
                 if (!all) return py::make_tuple(segs, py::none());
-                py::array_t<double> out({(py::ssize_t)flat.size(), (py::ssize_t)3});
-                for (size_t i = 0; i < flat.size(); ++i)
-                    for (int k = 0; k < 3; ++k) out.mutable_data()[i * 3 + k] = flat[i][k];
+                py::array_t<double> out = from_points(flat);
                 return py::make_tuple(segs, out);
             },
             py::arg("problems"), py::arg("timeLimit"))
@@ -556,10 +464,7 @@ PYBIND11_MODULE(online_traj_planner, m) {
                     ok = self.planOnce(s, g, samples, seed, path);
                 }
                 if (!ok) return py::none();
-                py::array_t<double> out({(py::ssize_t)path.size(), (py::ssize_t)3});
-                for (size_t i = 0; i < path.size(); ++i)
-                    for (int k = 0; k < 3; ++k) out.mutable_data()[i * 3 + k] = path[i][k];
-                return out;
+                return from_points(path);
             },
             py::arg("start"), py::arg("goal"), py::arg("samples"), py::arg("seed"))
         .def(
@@ -690,9 +595,7 @@ PYBIND11_MODULE(online_traj_planner, m) {
             }
             py::list out;
             for (const auto& r : res) {
-                py::array_t<double> wp({(py::ssize_t)r.waypoints.size(), (py::ssize_t)3});
-                for (size_t i = 0; i < r.waypoints.size(); ++i)
-                    for (int k = 0; k < 3; ++k) wp.mutable_data()[i * 3 + k] = r.waypoints[i][k];
+                py::array_t<double> wp = from_points(r.waypoints);
                 out.append(py::make_tuple(wp, from_matrix(r.trajectory), r.device));
             }
             return out;
@@ -727,10 +630,7 @@ PYBIND11_MODULE(online_traj_planner, m) {
         .def(
             "sample_traj",
             [](const epp::OnlineTrajGenerator& self, double t) {
-                std::vector<double> r = self.sampleTraj(t);
-                py::array_t<double> out((py::ssize_t)r.size());
-                std::memcpy(out.mutable_data(), r.data(), r.size() * sizeof(double));
-                return out;
+                return to_array<double>(self.sampleTraj(t));
             },
             py::arg("currentTime"))
         .def("get_traj_end_time", &epp::OnlineTrajGenerator::getTrajEndTime)
@@ -744,13 +644,7 @@ PYBIND11_MODULE(online_traj_planner, m) {
                      py::gil_scoped_release release;
                      self.plannedGatePasses(rows, times);
                  }
-                 py::array_t<int64_t> r((py::ssize_t)rows.size());
-                 py::array_t<double> t((py::ssize_t)times.size());
-                 for (size_t i = 0; i < rows.size(); ++i) {
-                     r.mutable_data()[i] = rows[i];
-                     t.mutable_data()[i] = times[i];
-                 }
-                 return py::make_tuple(r, t);
+                 return py::make_tuple(to_array<int64_t>(rows), to_array<double>(times));
              })
         .def("wait_for_update", &epp::OnlineTrajGenerator::waitForUpdate, py::call_guard<py::gil_scoped_release>())
         .def("recompute_counts",
@@ -767,10 +661,7 @@ PYBIND11_MODULE(online_traj_planner, m) {
             py::return_value_policy::reference_internal)
         .def("get_waypoints", [](const epp::OnlineTrajGenerator& self) {
             const auto c = self.getWaypoints();
-            py::array_t<double> out({(py::ssize_t)c.size(), (py::ssize_t)3});
-            for (size_t i = 0; i < c.size(); ++i)
-                for (int k = 0; k < 3; ++k) out.mutable_data()[i * 3 + k] = c[i][k];
-            return out;
+            return from_points(c);
         })
         .def("planner_stats", [](epp::OnlineTrajGenerator& self) {
             const auto& s = self.planner().lastStats();
@@ -803,9 +694,6 @@ PYBIND11_MODULE(online_traj_planner, m) {
         })
         .def("get_checkpoints", [](const epp::OnlineTrajGenerator& self) {
             const auto& c = self.getCheckpoints();
-            py::array_t<double> out({(py::ssize_t)c.size(), (py::ssize_t)3});
-            for (size_t i = 0; i < c.size(); ++i)
-                for (int k = 0; k < 3; ++k) out.mutable_data()[i * 3 + k] = c[i][k];
-            return out;
+            return from_points(c);
         });
 }

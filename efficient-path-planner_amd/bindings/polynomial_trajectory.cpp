@@ -41,6 +41,16 @@ static void read_waypoint_pins(py::object o, int k, py::ssize_t n, std::vector<u
     }
 }
 
+// The n rows a *_host call handed out (none when it failed: it raises) as an (n, 10) array, freed.
+static py::array_t<double> take_rows(epp_status rc, double* rows, int64_t n) {
+    if (rc == EPP_ERR_INVALID_ARGUMENT) throw std::invalid_argument(epp_last_error());
+    if (rc != EPP_OK) throw std::runtime_error(epp_last_error());
+    py::array_t<double> out({(py::ssize_t)n, (py::ssize_t)10});
+    if (n) std::memcpy(out.mutable_data(), rows, (size_t)n * 10 * sizeof(double));
+    epp_host_free(rows);
+    return out;
+}
+
 static py::array_t<double> generate_trajectory(py::array_t<double, py::array::c_style | py::array::forcecast> waypoints,
                                                double v_max, double a_max, double sampling_intervall,
                                                double start_time_offset, py::object initial_vel,
@@ -87,12 +97,7 @@ static py::array_t<double> generate_trajectory(py::array_t<double, py::array::c_
                                                           sampling_intervall, start_time_offset, mask.data(),
                                                           values.data(), &rows, &nr);
         }
-        if (rc == EPP_ERR_INVALID_ARGUMENT) throw std::invalid_argument(epp_last_error());
-        if (rc != EPP_OK) throw std::runtime_error(epp_last_error());
-        py::array_t<double> out({(py::ssize_t)nr, (py::ssize_t)10});
-        if (nr) std::memcpy(out.mutable_data(), rows, (size_t)nr * 10 * sizeof(double));
-        epp_host_free(rows);
-        return out;
+        return take_rows(rc, rows, nr);
     }
     // thrustLimits = (g, f_min, f_max, rate_max, cos_tilt_min): the fit also time-scaled until
     // its thrust, body rate and tilt are within them (epp_traj_scale_to_thrust_limits),
@@ -148,12 +153,7 @@ static py::array_t<double> generate_trajectory(py::array_t<double, py::array::c_
                  : epp_generate_trajectory_host(waypoints.data(), (int32_t)waypoints.shape(0), v_max, a_max,
                                                 sampling_intervall, start_time_offset, v0, a0, &rows, &n);
     }
-    if (rc == EPP_ERR_INVALID_ARGUMENT) throw std::invalid_argument(epp_last_error());
-    if (rc != EPP_OK) throw std::runtime_error(epp_last_error());
-    py::array_t<double> out({(py::ssize_t)n, (py::ssize_t)10});
-    if (n) std::memcpy(out.mutable_data(), rows, (size_t)n * 10 * sizeof(double));
-    epp_host_free(rows);
-    return out;
+    return take_rows(rc, rows, n);
 }
 
 // Trajectory::computeMaxVelocityAndAcceleration (src/trajectory.cpp:344-361) of the fit

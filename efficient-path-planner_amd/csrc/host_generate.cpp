@@ -1,7 +1,8 @@
 // host_generate.cpp — the C entry points of the single-track host calls: generateTrajectory
 // (and its variants with caller times and with the fused check) over the refit
 // (minsnap_refit.hip), the fits scaled to limits before the sampling (generate_scaled) and the
-// fit under the caller's constraints (generate_constrained).
+// fit under the caller's constraints (generate_constrained), which end in one row-sampling
+// tail (sample_fitted_rows).
 // Host code only: the kernels are enqueued through minsnap_kernels.h and the C ABI.
 #include <algorithm>
 #include <cstdlib>
@@ -41,6 +42,40 @@ epp_status generate_trajectory(const double* wp, int32_t n_wp, const double* tim
     return free_rows_on_failure(
         generate_trajectory_into(wp, n_wp, times, v_max, a_max, dt, t0, v0, a0, malloc_rows, rows_out, n_rows),
         rows_out);
+}
+
+// The end of generate_scaled and generate_constrained, once the fit's statuses have passed:
+// the host runs Trajectory::evaluateRange's sample recurrence on the fitted (scaled) times in
+// the pinned block (the exact row count), then the row sampler on c's stream into h_out, one
+// synchronisation, and the rows copied into a malloc'ed buffer the caller owns.
+epp_status sample_fitted_rows(StreamBufs& c, const double* h_T, const double* h_C, const int32_t* h_off, int M,
+                              double dt, const double* h_t0, double** rows_out, int64_t* n_rows) {
+    int64_t R = 0;
+    if (dt > 0) {
+        RangeIter it;
+        it.init(h_T, M);
+        R = range_count(it, dt);
+    }
+    if (!malloc_rows(rows_out, R)) {
+        set_error("generateTrajectory: out of host memory");
+        return EPP_ERR_RUNTIME;
+    }
+    if (R) {
+        epp_status rc = EPP_OK;
+        hipError_t e;
+        if ((e = c.ensure(0, (size_t)R * 80, 0)) != hipSuccess) rc = buffers_error(e);
+        if (!rc)
+            rc = launch_sample_rows_track(h_T, h_C, h_off, M, dt, h_t0, c.h_out.as<double>(), R, c.s,
+                                          "generateTrajectory");
+        if (!rc && (e = hipStreamSynchronize(c.s)) != hipSuccess) {
+            set_error(std::string("generateTrajectory: ") + hipGetErrorString(e));
+            rc = EPP_ERR_HIP;
+        }
+        if (rc) return free_rows_on_failure(rc, rows_out);
+        std::memcpy(*rows_out, c.h_out.p, (size_t)R * 80);
+    }
+    *n_rows = R;
+    return EPP_OK;
 }
 
 // generateTrajectory followed by Trajectory::scaleSegmentTimesToMeetConstraints
@@ -148,37 +183,9 @@ epp_status generate_scaled(const double* wp, int32_t n_wp, double v_max, double 
         return EPP_ERR_RUNTIME;
     }
     if (opt_out) *opt_out = TimeoptOut{h_cost[0], h_cost[1], h_st[4]};
-    int64_t R = 0;
-    if (dt > 0) {  // Trajectory::evaluateRange's recurrence on the scaled times (exact count)
-        RangeIter it;
-        it.init(h_T, M);
-        R = range_count(it, dt);
-    }
-    double* rows = (double*)std::malloc((size_t)std::max<int64_t>(R, 1) * 80);
-    if (!rows) {
-        set_error("generateTrajectory: out of host memory");
-        return EPP_ERR_RUNTIME;
-    }
-    if (R) {
-        rc = EPP_OK;
-        if ((e = c.ensure(0, (size_t)R * 80, 0)) != hipSuccess) rc = buffers_error(e);
-        if (!rc)
-            rc = launch_sample_rows_track(h_T, h_C, h_off, M, dt, h_t0, c.h_out.as<double>(), R, c.s,
-                                          "generateTrajectory");
-        if (!rc && (e = hipStreamSynchronize(c.s)) != hipSuccess) {
-            set_error(std::string("generateTrajectory: ") + hipGetErrorString(e));
-            rc = EPP_ERR_HIP;
-        }
-        if (rc) {
-            std::free(rows);
-            return rc;
-        }
-        std::memcpy(rows, c.h_out.p, (size_t)R * 80);
-    }
+    if ((rc = sample_fitted_rows(c, h_T, h_C, h_off, M, dt, h_t0, rows_out, n_rows))) return rc;
     if (scale_out) *scale_out = h_scale[0];
     if (scale_thrust) *scale_thrust = h_scale[1];
-    *rows_out = rows;
-    *n_rows = R;
     return EPP_OK;
 }
 
@@ -245,36 +252,7 @@ epp_status generate_constrained(const double* wp, int32_t n_wp, double v_max, do
         set_error(fit_status_message(h_st[0]));
         return EPP_ERR_RUNTIME;
     }
-    int64_t R = 0;
-    if (dt > 0) {  // Trajectory::evaluateRange's recurrence on the fit's times (exact count)
-        RangeIter it;
-        it.init(h_T, M);
-        R = range_count(it, dt);
-    }
-    double* rows = (double*)std::malloc((size_t)std::max<int64_t>(R, 1) * 80);
-    if (!rows) {
-        set_error("generateTrajectory: out of host memory");
-        return EPP_ERR_RUNTIME;
-    }
-    if (R) {
-        rc = EPP_OK;
-        if ((e = c.ensure(0, (size_t)R * 80, 0)) != hipSuccess) rc = buffers_error(e);
-        if (!rc)
-            rc = launch_sample_rows_track(h_T, h_C, h_off, M, dt, h_t0, c.h_out.as<double>(), R, c.s,
-                                          "generateTrajectory");
-        if (!rc && (e = hipStreamSynchronize(c.s)) != hipSuccess) {
-            set_error(std::string("generateTrajectory: ") + hipGetErrorString(e));
-            rc = EPP_ERR_HIP;
-        }
-        if (rc) {
-            std::free(rows);
-            return rc;
-        }
-        std::memcpy(rows, c.h_out.p, (size_t)R * 80);
-    }
-    *rows_out = rows;
-    *n_rows = R;
-    return EPP_OK;
+    return sample_fitted_rows(c, h_T, h_C, h_off, M, dt, h_t0, rows_out, n_rows);
 }
 
 }  // namespace

@@ -460,15 +460,37 @@ class World:
                 d_obb.download(np.int32, nt))
 
 
+def _take_rows(rows, n, cols=10) -> np.ndarray:
+    """The n rows a *_host call handed out as an (n, cols) array of its own; the call's buffer is
+    freed (epp_host_free)."""
+    out = np.ctypeslib.as_array(rows, shape=(n.value * cols,)).copy().reshape(-1, cols) if n.value \
+        else np.zeros((0, cols))
+    lib().epp_host_free(C.cast(rows, C.c_void_p))
+    return out
+
+
+def _pack_waypoints(tracks):
+    """A list of (W_k x 3) waypoint arrays as the batch calls take it: (wp float64[sum W_k, 3],
+    off int32[n + 1], n, the number of segments sum W_k - n)."""
+    tracks = [np.asarray(t, np.float64).reshape(-1, 3) for t in tracks]
+    wp = np.ascontiguousarray(np.concatenate(tracks))
+    off = np.zeros(len(tracks) + 1, np.int32)
+    off[1:] = np.cumsum([len(t) for t in tracks])
+    return wp, off, len(tracks), int(off[-1]) - len(tracks)
+
+
+def _split_tracks(T, Cf, off):
+    """The per-segment arrays T and Cf (either may be None) of a batch with waypoint offsets off
+    as per-track lists: track k's segments are off[k] - k .. off[k + 1] - k - 2."""
+    spans = [(int(off[k]) - k, max(int(off[k]) - k, int(off[k + 1]) - k - 1)) for k in range(len(off) - 1)]
+    return tuple(None if a is None else [a[i:j] for i, j in spans] for a in (T, Cf))
+
+
 def minsnap_batch(tracks, v_max, a_max, v0=None, a0=None):
     """epp_minsnap_batch on a list of (W_k x 3) waypoint arrays.
 
     Returns (seg_times list, coeffs list [M_k x 3 x 10], status array)."""
-    wp = np.ascontiguousarray(np.concatenate([np.asarray(t, np.float64).reshape(-1, 3) for t in tracks]))
-    off = np.zeros(len(tracks) + 1, np.int32)
-    off[1:] = np.cumsum([len(t) for t in tracks])
-    nt = len(tracks)
-    nseg = int(off[-1]) - nt
+    wp, off, nt, nseg = _pack_waypoints(tracks)
     d_wp, d_off = DeviceBuffer.from_array(wp), DeviceBuffer.from_array(off)
     d_v0 = DeviceBuffer.from_array(np.ascontiguousarray(v0, np.float64)) if v0 is not None else None
     d_a0 = DeviceBuffer.from_array(np.ascontiguousarray(a0, np.float64)) if a0 is not None else None
@@ -480,11 +502,7 @@ def minsnap_batch(tracks, v_max, a_max, v0=None, a0=None):
     T = d_T.download(np.float64, nseg)
     Cf = d_C.download(np.float64, nseg * 30).reshape(nseg, 3, 10)
     st = d_st.download(np.int32, nt)
-    Ts, Cs = [], []
-    for k in range(nt):
-        a, b = int(off[k]) - k, int(off[k + 1]) - k - 1
-        Ts.append(T[a:max(a, b)])
-        Cs.append(Cf[a:max(a, b)])
+    Ts, Cs = _split_tracks(T, Cf, off)
     return Ts, Cs, st
 
 
@@ -492,11 +510,7 @@ def minsnap_batch_times(tracks, times, v0=None, a0=None):
     """epp_minsnap_batch_times: as minsnap_batch with the caller's segment times (a list
     of (W_k - 1) arrays; setupFromVertices(vertices, segment_times)).  Returns (coeffs
     list, status array)."""
-    wp = np.ascontiguousarray(np.concatenate([np.asarray(t, np.float64).reshape(-1, 3) for t in tracks]))
-    off = np.zeros(len(tracks) + 1, np.int32)
-    off[1:] = np.cumsum([len(t) for t in tracks])
-    nt = len(tracks)
-    nseg = int(off[-1]) - nt
+    wp, off, nt, nseg = _pack_waypoints(tracks)
     T = np.ascontiguousarray(np.concatenate([np.asarray(t, np.float64).ravel() for t in times]))
     assert len(T) == nseg
     d_wp, d_off, d_T = DeviceBuffer.from_array(wp), DeviceBuffer.from_array(off), DeviceBuffer.from_array(T)
@@ -508,7 +522,7 @@ def minsnap_batch_times(tracks, times, v0=None, a0=None):
     sync()
     Cf = d_C.download(np.float64, nseg * 30).reshape(nseg, 3, 10)
     st = d_st.download(np.int32, nt)
-    return [Cf[int(off[k]) - k:int(off[k + 1]) - k - 1] for k in range(nt)], st
+    return _split_tracks(None, Cf, off)[1], st
 
 
 def minsnap_batch_constrained(tracks, v_max, a_max, masks, values, times=None):
@@ -524,11 +538,8 @@ def minsnap_batch_constrained(tracks, v_max, a_max, masks, values, times=None):
         check(lib().epp_minsnap_batch_constrained(None, None, 0, float(v_max), float(a_max), None, None, None,
                                                   None, None, None, None))
         return [], [], np.zeros(0, np.int32)
-    wp = np.ascontiguousarray(np.concatenate([np.asarray(t, np.float64).reshape(-1, 3) for t in tracks]))
-    off = np.zeros(nt + 1, np.int32)
-    off[1:] = np.cumsum([len(t) for t in tracks])
-    nw = int(off[-1])
-    nseg = nw - nt
+    wp, off, nt, nseg = _pack_waypoints(tracks)
+    nw = len(wp)
     mask = np.ascontiguousarray(np.concatenate([np.asarray(m, np.uint8).ravel() for m in masks]))
     val = np.ascontiguousarray(np.concatenate([np.asarray(v, np.float64).reshape(-1, 12) for v in values]))
     if len(mask) != nw or len(val) != nw:
@@ -551,11 +562,7 @@ def minsnap_batch_constrained(tracks, v_max, a_max, masks, values, times=None):
     T = d_T.download(np.float64, nseg)
     Cf = d_C.download(np.float64, nseg * 30).reshape(nseg, 3, 10)
     st = d_st.download(np.int32, nt)
-    Ts, Cs = [], []
-    for k in range(nt):
-        a, b = int(off[k]) - k, int(off[k + 1]) - k - 1
-        Ts.append(T[a:max(a, b)])
-        Cs.append(Cf[a:max(a, b)])
+    Ts, Cs = _split_tracks(T, Cf, off)
     return Ts, Cs, st
 
 
@@ -575,12 +582,7 @@ def generate_trajectory_constrained(waypoints, v_max, a_max, dt, mask, values, s
     check(lib().epp_generate_trajectory_constrained_host(_ptr(wp), len(wp), float(v_max), float(a_max),
                                                          _ptr(T) if T is not None else None, float(dt), float(t0),
                                                          _ptr(mask), _ptr(val), C.byref(rows), C.byref(n)))
-    if n.value == 0:
-        lib().epp_host_free(C.cast(rows, C.c_void_p))
-        return np.zeros((0, 10))
-    out = np.ctypeslib.as_array(rows, shape=(n.value * 10,)).copy().reshape(-1, 10)
-    lib().epp_host_free(C.cast(rows, C.c_void_p))
-    return out
+    return _take_rows(rows, n)
 
 
 def generate_trajectory_times(waypoints, seg_times, dt, t0=0.0, v0=(0, 0, 0), a0=(0, 0, 0)) -> np.ndarray:
@@ -593,12 +595,7 @@ def generate_trajectory_times(waypoints, seg_times, dt, t0=0.0, v0=(0, 0, 0), a0
     n = C.c_int64(0)
     check(lib().epp_generate_trajectory_times_host(_ptr(wp), len(wp), _ptr(T), float(dt), float(t0), _ptr(v0),
                                                    _ptr(a0), C.byref(rows), C.byref(n)))
-    if n.value == 0:
-        lib().epp_host_free(C.cast(rows, C.c_void_p))
-        return np.zeros((0, 10))
-    out = np.ctypeslib.as_array(rows, shape=(n.value * 10,)).copy().reshape(-1, 10)
-    lib().epp_host_free(C.cast(rows, C.c_void_p))
-    return out
+    return _take_rows(rows, n)
 
 
 def generate_trajectory(waypoints, v_max, a_max, dt, t0=0.0, v0=(0, 0, 0), a0=(0, 0, 0)) -> np.ndarray:
@@ -610,12 +607,7 @@ def generate_trajectory(waypoints, v_max, a_max, dt, t0=0.0, v0=(0, 0, 0), a0=(0
     n = C.c_int64(0)
     check(lib().epp_generate_trajectory_host(_ptr(wp), len(wp), float(v_max), float(a_max), float(dt), float(t0),
                                              _ptr(v0), _ptr(a0), C.byref(rows), C.byref(n)))
-    if n.value == 0:
-        lib().epp_host_free(C.cast(rows, C.c_void_p))
-        return np.zeros((0, 10))
-    out = np.ctypeslib.as_array(rows, shape=(n.value * 10,)).copy().reshape(-1, 10)
-    lib().epp_host_free(C.cast(rows, C.c_void_p))
-    return out
+    return _take_rows(rows, n)
 
 
 def _upload_tracks(Ts, Cs):
@@ -854,11 +846,7 @@ def scale_to_limits(Ts, Cs, v_max, a_max):
     sync()
     T = d_T.download(np.float64, nseg)
     Cf = d_C.download(np.float64, nseg * 30).reshape(nseg, 3, 10)
-    Tn, Cn = [], []
-    for k in range(nt):
-        a, b = int(off[k]) - k, int(off[k + 1]) - k - 1
-        Tn.append(T[a:max(a, b)])
-        Cn.append(Cf[a:max(a, b)])
+    Tn, Cn = _split_tracks(T, Cf, off)
     return Tn, Cn, d_sc.download(np.float64, nt), d_st.download(np.int32, nt)
 
 
@@ -875,8 +863,7 @@ def generate_trajectory_limited(waypoints, v_max, a_max, dt, t0=0.0, v0=(0, 0, 0
     check(lib().epp_generate_trajectory_limited_host(_ptr(wp), len(wp), float(v_max), float(a_max), float(dt),
                                                      float(t0), _ptr(v0), _ptr(a0), C.byref(rows), C.byref(n),
                                                      C.byref(scale)))
-    out = np.ctypeslib.as_array(rows, shape=(n.value * 10,)).copy().reshape(-1, 10) if n.value else np.zeros((0, 10))
-    lib().epp_host_free(C.cast(rows, C.c_void_p))
+    out = _take_rows(rows, n)
     return (out, scale.value) if return_scale else out
 
 
@@ -909,11 +896,7 @@ def scale_to_thrust_limits(Ts, Cs, g, f_min, f_max, rate_max, cos_tilt_min):
     sync()
     T = d_T.download(np.float64, nseg)
     Cf = d_C.download(np.float64, nseg * 30).reshape(nseg, 3, 10)
-    Tn, Cn = [], []
-    for k in range(nt):
-        a, b = int(off[k]) - k, int(off[k + 1]) - k - 1
-        Tn.append(T[a:max(a, b)])
-        Cn.append(Cf[a:max(a, b)])
+    Tn, Cn = _split_tracks(T, Cf, off)
     return Tn, Cn, d_sc.download(np.float64, nt), d_st.download(np.int32, nt), d_vi.download(np.int32, nt)
 
 
@@ -928,10 +911,7 @@ def snap_cost(Ts, Cs):
 
 
 def _upload_fit_inputs(tracks, times, v0, a0):
-    wp = np.ascontiguousarray(np.concatenate([np.asarray(t, np.float64).reshape(-1, 3) for t in tracks]))
-    off = np.zeros(len(tracks) + 1, np.int32)
-    off[1:] = np.cumsum([len(np.asarray(t).reshape(-1, 3)) for t in tracks])
-    nseg = int(off[-1]) - len(tracks)
+    wp, off, _, nseg = _pack_waypoints(tracks)
     T = np.ascontiguousarray(np.concatenate([np.asarray(t, np.float64).ravel() for t in times] + [np.zeros(0)]))
     assert len(T) == nseg
     d_wp, d_off = DeviceBuffer.from_array(wp), DeviceBuffer.from_array(off)
@@ -953,8 +933,7 @@ def time_gradient(tracks, times, h=0.1, t_min=0.1, v0=None, a0=None):
                                           d_g.ptr, d_st.ptr, None))
     sync()
     g = d_g.download(np.float64, nseg)
-    return (d_J.download(np.float64, nt), [g[int(off[k]) - k:max(int(off[k]) - k, int(off[k + 1]) - k - 1)]
-                                           for k in range(nt)], d_st.download(np.int32, nt))
+    return d_J.download(np.float64, nt), _split_tracks(g, None, off)[0], d_st.download(np.int32, nt)
 
 
 def optimize_times(tracks, times, params=None, v0=None, a0=None):
@@ -972,11 +951,7 @@ def optimize_times(tracks, times, params=None, v0=None, a0=None):
     sync()
     T = d_T.download(np.float64, nseg)
     Cf = d_C.download(np.float64, nseg * 30).reshape(nseg, 3, 10)
-    Tn, Cn = [], []
-    for k in range(nt):
-        a, b = int(off[k]) - k, int(off[k + 1]) - k - 1
-        Tn.append(T[a:max(a, b)])
-        Cn.append(Cf[a:max(a, b)])
+    Tn, Cn = _split_tracks(T, Cf, off)
     return (Tn, Cn, d_J0.download(np.float64, nt), d_J1.download(np.float64, nt), d_it.download(np.int32, nt),
             d_st.download(np.int32, nt))
 
@@ -1000,8 +975,7 @@ def generate_trajectory_timeopt(waypoints, v_max, a_max, dt, params=None, t0=0.0
                                                      1 if enforce_va else 0, _ptr(tl) if tl is not None else None,
                                                      C.byref(rows), C.byref(n), C.byref(j0), C.byref(j1),
                                                      C.byref(it)))
-    out = np.ctypeslib.as_array(rows, shape=(n.value * 10,)).copy().reshape(-1, 10) if n.value else np.zeros((0, 10))
-    lib().epp_host_free(C.cast(rows, C.c_void_p))
+    out = _take_rows(rows, n)
     return (out, j0.value, j1.value, it.value) if return_costs else out
 
 
@@ -1022,8 +996,7 @@ def generate_trajectory_flyable(waypoints, v_max, a_max, dt, limits, t0=0.0, v0=
                                                      float(t0), _ptr(v0), _ptr(a0), 1 if enforce_va else 0, g, f_min,
                                                      f_max, rate_max, cos_tilt_min, C.byref(rows), C.byref(n),
                                                      C.byref(s_va), C.byref(s_th)))
-    out = np.ctypeslib.as_array(rows, shape=(n.value * 10,)).copy().reshape(-1, 10) if n.value else np.zeros((0, 10))
-    lib().epp_host_free(C.cast(rows, C.c_void_p))
+    out = _take_rows(rows, n)
     return (out, s_va.value, s_th.value) if return_scales else out
 
 
@@ -1042,8 +1015,7 @@ def check_and_generate_trajectory(world: "World", check_xyz, min_distance, waypo
                                                        _ptr(flags), _ptr(wp), len(wp), float(v_max), float(a_max),
                                                        float(dt), float(t0), _ptr(v0), _ptr(a0), C.byref(rows),
                                                        C.byref(n)))
-    out = np.ctypeslib.as_array(rows, shape=(n.value * 10,)).copy().reshape(-1, 10) if n.value else np.zeros((0, 10))
-    lib().epp_host_free(C.cast(rows, C.c_void_p))
+    out = _take_rows(rows, n)
     return flags[:len(pts)], out
 
 
@@ -1057,12 +1029,7 @@ def optimal_trajectory(waypoints, v_max, a_max, dt, t0=0.0, max_deviation=0.1, p
     check(lib().epp_optimal_trajectory_host(_ptr(wp), len(wp), _ptr(pre) if len(pre) else None, len(pre),
                                             float(v_max), float(a_max), float(dt), float(t0), float(max_deviation),
                                             C.byref(rows), C.byref(n)))
-    if n.value == 0:
-        lib().epp_host_free(C.cast(rows, C.c_void_p))
-        return np.zeros((0, 11))
-    out = np.ctypeslib.as_array(rows, shape=(n.value * 11,)).copy().reshape(-1, 11)
-    lib().epp_host_free(C.cast(rows, C.c_void_p))
-    return out
+    return _take_rows(rows, n, 11)
 
 
 def spline_trajectory(waypoints, max_t, dt, t0=0.0) -> np.ndarray:
@@ -1073,9 +1040,7 @@ def spline_trajectory(waypoints, max_t, dt, t0=0.0) -> np.ndarray:
     n = C.c_int64(0)
     check(lib().epp_spline_trajectory_host(_ptr(wp), len(wp), float(max_t), float(t0), float(dt),
                                            C.byref(rows), C.byref(n)))
-    out = np.ctypeslib.as_array(rows, shape=(n.value * 10,)).copy().reshape(-1, 10) if n.value else np.zeros((0, 10))
-    lib().epp_host_free(C.cast(rows, C.c_void_p))
-    return out
+    return _take_rows(rows, n)
 
 
 def sample_uniform(seed: int, lo, hi, n: int, start: int = 0) -> np.ndarray:
