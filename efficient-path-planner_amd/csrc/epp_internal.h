@@ -69,7 +69,7 @@ epp_status check_and_generate_into(const FusedCheck* chk, const double* wp, int3
                                    const double a0[3], double* (*alloc)(void*, int64_t), void* ctx, int64_t* n_rows);
 // The planner's edge mask folded into the k-NN-table motion check (k_motions_v5, IDX):
 // failed entries of nbr_w -> -1, out16 (optional) the masked table as u16, count[0] / [1]
-// += kept edges / kept edges into node `target`.  count == nullptr: no mask.
+// += kept edges / kept edges into node `target`.  Neither count nor out16: no mask.
 struct MotionMask {
     int32_t* nbr_w = nullptr;
     uint16_t* out16 = nullptr;

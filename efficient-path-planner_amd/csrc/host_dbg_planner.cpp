@@ -7,6 +7,9 @@
 //                         node list copied out.  No PathPlanner, no solver threads, no
 //                         fallback: what the stages wrote is what the caller sees.
 //   epp_dbg_reverse_csr : epp::reverse_csr of a device table, roff / radj / radj16 copied out.
+//   epp_dbg_knn_motions_masked / _rows : epp::check_knn_motions_masked / _rows on the caller's
+//                         device buffers, nothing allocated or cleared: what k_motions_v5's
+//                         MotionMask tail writes, and leaves alone, is what the caller reads.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -175,4 +178,35 @@ extern "C" epp_status epp_dbg_reverse_csr(const int32_t* nbr, int32_t n, int32_t
     if (narrow && ne > 0 && hipMemcpy(radj16, adj16.p, (size_t)ne * 2, hipMemcpyDeviceToHost) != hipSuccess)
         return hip_fail("epp_dbg_reverse_csr");
     return EPP_OK;
+}
+
+// epp::check_knn_motions_masked on the caller's device buffers (nbr is rewritten in place);
+// the callee's status, unchanged.
+extern "C" epp_status epp_dbg_knn_motions_masked(const epp_world* world, const double* nodes, int32_t* nbr, int32_t n,
+                                                 int32_t k, int32_t can_pass_gate, uint8_t* valid, uint16_t* out16,
+                                                 int32_t target, int64_t* count, void* stream) {
+    return check_knn_motions_masked(world, nodes, nbr, n, k, can_pass_gate, valid, out16, target, count, stream);
+}
+
+extern "C" int32_t epp_dbg_knn_motions_rows_supported(const epp_world* world) {
+    return knn_motions_rows_supported(world) ? 1 : 0;
+}
+
+// epp::check_knn_motions_rows on the caller's device buffers, the marks built as
+// plan_batch_launch builds them (mark / pkept / pgoal / ns_log / nprob); mark == NULL: no
+// marks (the packed rows of one problem), pkept / pgoal / ns_log / nprob are then unused.
+// The callee's status, unchanged.
+extern "C" epp_status epp_dbg_knn_motions_rows(const epp_world* world, const double* nodes, int32_t* rows32,
+                                               const int32_t* ids32, const int64_t* rows_n, int32_t cap, int32_t k,
+                                               int32_t can_pass_gate, uint8_t* valid, uint16_t* out16, int32_t target,
+                                               int64_t* count, uint8_t* mark, uint64_t* pkept, uint64_t* pgoal,
+                                               int32_t ns_log, int32_t nprob, void* stream) {
+    MotionMask marks;
+    marks.mark = mark;
+    marks.pkept = reinterpret_cast<unsigned long long*>(pkept);
+    marks.pgoal = reinterpret_cast<unsigned long long*>(pgoal);
+    marks.ns_log = ns_log;
+    marks.nprob = nprob;
+    return check_knn_motions_rows(world, nodes, rows32, ids32, rows_n, cap, k, can_pass_gate, valid, out16, target,
+                                  count, stream, mark ? &marks : nullptr);
 }

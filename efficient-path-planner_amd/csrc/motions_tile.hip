@@ -33,7 +33,7 @@ constexpr int kQueueV5 = 256;
 // node e / kk to node nbr[e] (s1 = the nodes; a missing neighbour, -1, is the degenerate
 // edge from the node to itself), as epp_knn_edges would lay them out.
 //
-// MotionMask (IDX, count != nullptr): the planner's edge mask folded in -- a failed motion's
+// MotionMask (IDX, count or out16 given): the planner's edge mask folded in -- a failed motion's
 // table entry becomes -1, out16 (if given) receives the masked table as u16 (0xFFFF: no
 // edge), and count[0] / count[1] gain the kept edges / those into node `target` (one atomic
 // per workgroup), as k_mask_edges_count (planner.hip) would after the launch.

@@ -156,6 +156,10 @@ def lib() -> C.CDLL:
             "epp_dbg_plan_batch": (i32, [vp, i32, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32,
                                          vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, i32, vp, vp]),
             "epp_dbg_reverse_csr": (i32, [vp, i32, i32, vp, vp, vp]),
+            "epp_dbg_knn_motions_masked": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, i32, vp, vp]),
+            "epp_dbg_knn_motions_rows_supported": (i32, [vp]),
+            "epp_dbg_knn_motions_rows": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, i32,
+                                               i32, vp]),
         }
         for name, (res, args) in sig.items():
             if os.environ.get("EPP_LIB") and not hasattr(l, name):
@@ -1200,6 +1204,84 @@ def dbg_reverse_csr(nbr: np.ndarray):
     check(lib().epp_dbg_reverse_csr(d_n.ptr, n, k, _ptr(roff), _ptr(radj), _ptr(radj16) if radj16 is not None else None))
     ne = int(roff[n])
     return roff, radj[:ne].copy(), (radj16[:ne].copy() if radj16 is not None else None)
+
+
+def _dbg_dev(dev: dict, name: str, a, upload: bool):
+    """The device buffer of argument `name`: None for None (a NULL pointer), a DeviceBuffer as
+    it is, else dev[name], created and filled from the array a on first use and refilled when
+    upload is set (else it keeps what it holds)."""
+    if a is None or isinstance(a, DeviceBuffer):
+        return a
+    b = dev.get(name)
+    if b is None or b.nbytes < a.nbytes:
+        b = dev[name] = DeviceBuffer.from_array(a)
+    elif upload:
+        b.upload(a)
+    return b
+
+
+def _dbg_back(b, a):
+    """The whole of buffer b as an array shaped and typed like a (None for None)."""
+    return None if b is None else b.download(a.dtype, a.size).reshape(a.shape)
+
+
+def dbg_knn_motions_masked(world: "World", nodes, nbr: np.ndarray, can_pass_gate, target: int, valid, out16, count,
+                           dev: dict | None = None, upload: bool = True) -> dict:
+    """epp_dbg_knn_motions_masked (epp::check_knn_motions_masked): the table nbr (n x k int32)
+    over nodes (n x 3, or a DeviceBuffer) with the caller's prefill of every output -- valid
+    (n k u8), out16 (n k u16, None: NULL), count (2 i64, None: NULL).  Everything is uploaded,
+    the entry runs and every buffer is downloaded whole: dict(rc = the status, nbr = the
+    rewritten table, valid, out16, count).  dev: a dict that keeps the device buffers between
+    calls; upload=False then runs on what they hold."""
+    dev = {} if dev is None else dev
+    nbr = np.ascontiguousarray(nbr, np.int32)
+    n, k = nbr.shape
+    host = dict(nodes=nodes if isinstance(nodes, DeviceBuffer) else np.ascontiguousarray(nodes, np.float64),
+                nbr=nbr, valid=None if valid is None else np.ascontiguousarray(valid, np.uint8),
+                out16=None if out16 is None else np.ascontiguousarray(out16, np.uint16),
+                count=None if count is None else np.ascontiguousarray(count, np.int64))
+    d = {name: _dbg_dev(dev, name, a, upload) for name, a in host.items()}
+    p = {name: None if b is None else b.ptr for name, b in d.items()}
+    rc = lib().epp_dbg_knn_motions_masked(world.handle, p["nodes"], p["nbr"], n, k, 1 if can_pass_gate else 0,
+                                          p["valid"], p["out16"], int(target), p["count"], None)
+    sync()
+    return dict(rc=rc, **{name: _dbg_back(d[name], host[name]) for name in ("nbr", "valid", "out16", "count")})
+
+
+def dbg_knn_motions_rows_supported(world: "World") -> bool:
+    """epp_dbg_knn_motions_rows_supported (epp::knn_motions_rows_supported)."""
+    return bool(lib().epp_dbg_knn_motions_rows_supported(world.handle))
+
+
+def dbg_knn_motions_rows(world: "World", nodes, rows32: np.ndarray, ids32, rows_n: int, can_pass_gate, target: int,
+                         valid, out16, count, mark, pkept, pgoal, ns_log: int, nprob: int,
+                         dev: dict | None = None, upload: bool = True) -> dict:
+    """epp_dbg_knn_motions_rows (epp::check_knn_motions_rows, the marks as plan_batch_launch
+    builds them): the packed rows rows32 (cap x k int32, row r = node ids32[r], the first
+    rows_n of them live) over nodes (a DeviceBuffer, or an array), with the caller's prefill of
+    every output -- valid (cap k u8), out16 (cap k u16), count (2 i64), mark (u8 per node id),
+    pkept / pgoal (u64 per problem, and past nprob as far as the caller likes); None: NULL.
+    Everything is uploaded, the entry runs and every buffer is downloaded whole:
+    dict(rc, rows32, ids32, rows_n, valid, out16, count, mark, pkept, pgoal).  dev / upload: as
+    dbg_knn_motions_masked."""
+    dev = {} if dev is None else dev
+    rows32 = np.ascontiguousarray(rows32, np.int32)
+    cap, k = rows32.shape
+
+    def arr(a, dtype):
+        return None if a is None else np.ascontiguousarray(a, dtype)
+
+    host = dict(nodes=nodes if isinstance(nodes, DeviceBuffer) else np.ascontiguousarray(nodes, np.float64),
+                rows32=rows32, ids32=arr(ids32, np.int32), rows_n=np.array([rows_n], np.int64),
+                valid=arr(valid, np.uint8), out16=arr(out16, np.uint16), count=arr(count, np.int64),
+                mark=arr(mark, np.uint8), pkept=arr(pkept, np.uint64), pgoal=arr(pgoal, np.uint64))
+    d = {name: _dbg_dev(dev, name, a, upload) for name, a in host.items()}
+    p = {name: None if b is None else b.ptr for name, b in d.items()}
+    rc = lib().epp_dbg_knn_motions_rows(world.handle, p["nodes"], p["rows32"], p["ids32"], p["rows_n"], cap, k,
+                                        1 if can_pass_gate else 0, p["valid"], p["out16"], int(target), p["count"],
+                                        p["mark"], p["pkept"], p["pgoal"], int(ns_log), int(nprob), None)
+    sync()
+    return dict(rc=rc, **{name: _dbg_back(d[name], host[name]) for name in host if name != "nodes"})
 
 
 class Comm:
