@@ -353,6 +353,61 @@ PYBIND11_MODULE(online_traj_planner, m) {
             },
             py::arg("s1"), py::arg("s2"), py::arg("can_pass_gate") = false)
         .def(
+            "edge_clearances",  // distance between every edge s1[i] -> s2[i] and the nearest collision OBB (this build)
+            [](const epp::PathPlanner& self, const py::object& s1, const py::object& s2) {
+                Matrix a = to_matrix(s1), b = to_matrix(s2);
+                if (a.cols != 3 || b.cols != 3 || a.rows != b.rows)
+                    throw std::invalid_argument("s1 and s2 must be (n, 3) arrays of the same length");
+                std::vector<double> x1(a.rows * 3), x2(a.rows * 3);
+                for (size_t i = 0; i < a.rows; ++i)
+                    for (size_t k = 0; k < 3; ++k) {
+                        x1[3 * i + k] = a(i, k);
+                        x2[3 * i + k] = b(i, k);
+                    }
+                py::array_t<double> d((py::ssize_t)a.rows), t((py::ssize_t)a.rows);
+                py::array_t<int32_t> o((py::ssize_t)a.rows);
+                double* dp = d.mutable_data();
+                double* tp = t.mutable_data();
+                int32_t* op = o.mutable_data();
+                {
+                    py::gil_scoped_release release;
+                    self.worldPtr->edgeClearances(x1.data(), x2.data(), (int64_t)a.rows, dp, tp, op);
+                }
+                return py::make_tuple(d, t, o);
+            },
+            py::arg("s1"), py::arg("s2"))
+        .def(
+            "path_clearance",  // the room a waypoint polyline leaves: (distance, edge, t, nearest OBB) (this build)
+            [](const epp::PathPlanner& self, const py::object& path) {
+                const std::vector<Vec3> wp = read_waypoints(path);
+                long edge = -1;
+                double t = -1.0, dist;
+                int nearest = -1;
+                {
+                    py::gil_scoped_release release;
+                    dist = self.pathClearance(wp, &edge, &t, &nearest);
+                }
+                return py::make_tuple(dist, edge, t, nearest);
+            },
+            py::arg("path"))
+        .def(
+            "candidate_swept_clearances",  // fit + closest approach of the chords of K waypoint sets (this build)
+            [](const epp::PathPlanner& self, const std::vector<py::object>& waypointSets, double vMax, double aMax,
+               double samplingInterval) {
+                const std::vector<std::vector<Vec3>> sets = read_waypoint_sets(waypointSets);
+                std::vector<double> clearance, ts, times;
+                std::vector<long> chords;
+                std::vector<int> nearest;
+                {
+                    py::gil_scoped_release release;
+                    self.candidateSweptClearances(sets, vMax, aMax, samplingInterval, clearance, &chords, &ts, &times,
+                                                  &nearest);
+                }
+                return py::make_tuple(to_array<double>(clearance), to_array<int64_t>(chords), to_array<double>(ts),
+                                      to_array<double>(times), to_array<int32_t>(nearest));
+            },
+            py::arg("waypoint_sets"), py::arg("v_max"), py::arg("a_max"), py::arg("sampling_interval"))
+        .def(
             "check_point_validity",
             [](const epp::PathPlanner& self, const py::object& p, bool canPassGate) {
                 return self.worldPtr->checkPointValidity(to_vec3(p), canPassGate);

@@ -282,6 +282,64 @@ void PathPlanner::candidateClearances(const std::vector<std::vector<Vec3>>& sets
     if (nearest) nearest->assign(near.begin(), near.end());
 }
 
+// The closest approach of every fitted track's chords (epp_traj_chord_clearance_batch): the
+// distance, the chord, the parameter along it, the time of that point and the nearest OBB.
+void PathPlanner::candidateSweptClearances(const std::vector<std::vector<Vec3>>& sets, double v_max, double a_max,
+                                           double dt, std::vector<double>& clearance, std::vector<long>* chord,
+                                           std::vector<double>* t, std::vector<double>* time,
+                                           std::vector<int>* nearest) const {
+    CandidateBatch b("candidateSweptClearances", sets);
+    clearance.assign(b.n, HUGE_VAL);
+    if (chord) chord->assign(b.n, -1);
+    if (t) t->assign(b.n, -1.0);
+    if (time) time->assign(b.n, -1.0);
+    if (nearest) nearest->assign(b.n, -1);
+    if (b.n == 0) return;
+    const Part<double> p_clr = b.part<double>(b.n), p_t = b.part<double>(b.n), p_time = b.part<double>(b.n);
+    const Part<int64_t> p_chord = b.part<int64_t>(b.n);
+    const Part<int32_t> p_near = b.part<int32_t>(b.n);
+    b.fit(v_max, a_max);
+    b.need(epp_traj_chord_clearance_batch(worldPtr->device(), b.d_T(), b.d_C(), b.d_off(), b.count(), dt, b.dev(p_clr),
+                                          b.dev(p_chord), b.dev(p_t), b.dev(p_time), b.dev(p_near), b.stream()));
+    std::vector<double> clr(b.n), ts(b.n), times(b.n);
+    std::vector<int64_t> chords(b.n);
+    std::vector<int32_t> near(b.n);
+    b.fetch(p_chord, chords.data());
+    b.fetch(p_t, ts.data());
+    b.fetch(p_time, times.data());
+    b.fetch(p_clr, clr.data());
+    b.fetch(p_near, near.data());
+    b.finish();
+    clearance = clr;
+    if (chord) chord->assign(chords.begin(), chords.end());
+    if (t) *t = ts;
+    if (time) *time = times;
+    if (nearest) nearest->assign(near.begin(), near.end());
+}
+
+// The room a waypoint polyline leaves: the minimum of World::edgeClearances over its edges, the
+// earliest edge among equals.
+double PathPlanner::pathClearance(const std::vector<Vec3>& path, long* edge, double* t, int* nearest) const {
+    if (path.size() < 2) throw std::invalid_argument("pathClearance: a path has at least two points");
+    std::vector<double> xyz;
+    flatten(path, xyz);
+    const int64_t n = (int64_t)path.size() - 1;
+    std::vector<double> dist(n), ts(n);
+    std::vector<int32_t> near(n);
+    worldPtr->edgeClearances(xyz.data(), xyz.data() + 3, n, dist.data(), ts.data(), near.data());
+    int64_t j = -1;
+    double best = HUGE_VAL;
+    for (int64_t i = 0; i < n; ++i)
+        if (dist[i] < best) {
+            best = dist[i];
+            j = i;
+        }
+    if (edge) *edge = (long)j;
+    if (t) *t = j < 0 ? -1.0 : ts[j];
+    if (nearest) *nearest = j < 0 ? -1 : near[j];
+    return best;
+}
+
 // The gate centre and cos / sin of the yaw per gate row: getGateCenterAndNormal's centre
 // (src/OnlineTrajGenerator.cpp:50-70) and checkGatePassed's c, s (:236).
 Matrix PathPlanner::gateFrames(const Matrix& gates) const {

@@ -223,6 +223,30 @@ void World::firstHits(const double* s1, const double* s2, int64_t n, bool canPas
     if (obb) std::memcpy(obb, out.data() + (size_t)n * 8, (size_t)n * 4);
 }
 
+void World::edgeClearances(const double* s1, const double* s2, int64_t n, double* dist, double* t,
+                           int32_t* nearest) const {
+    if (n <= 0) return;
+    if (!device()) {  // an empty world: nothing to be near
+        for (int64_t i = 0; i < n; ++i) {
+            dist[i] = HUGE_VAL;
+            if (t) t[i] = -1.0;
+            if (nearest) nearest[i] = -1;
+        }
+        return;
+    }
+    // one output block per call: [dist (n f64) | t (n f64) | nearest (n i32)], 20 bytes per query
+    const double* in[2] = {s1, s2};
+    std::vector<uint8_t> out((size_t)n * 20);
+    query(n, 2, [&](const double* const* d, uint8_t* o, void* st) {
+        check(epp_motions_clearance(device(), d[0], d[1], n, reinterpret_cast<double*>(o),
+                                    reinterpret_cast<double*>(o + (size_t)n * 8),
+                                    reinterpret_cast<int32_t*>(o + (size_t)n * 16), st), "edgeClearances");
+    }, [](const double* const*, uint8_t*, void*) { return false; }, in, out.data(), 20);
+    std::memcpy(dist, out.data(), (size_t)n * 8);
+    if (t) std::memcpy(t, out.data() + (size_t)n * 8, (size_t)n * 8);
+    if (nearest) std::memcpy(nearest, out.data() + (size_t)n * 16, (size_t)n * 4);
+}
+
 template <typename Launch, typename Small>
 void World::query(int64_t n, int n_in, Launch&& launch, Small&& small, const double* const* in, uint8_t* out,
                   size_t out_item) const {

@@ -1,5 +1,6 @@
 // traj_walk.h — the walk over fitted tracks that every k_traj_* kernel runs (trajcheck.hip:
-// k_traj_check, k_traj_sweep, k_traj_first_hit, k_traj_clearance; gate_pass.hip: k_traj_gates;
+// k_traj_check, k_traj_sweep, k_traj_first_hit, k_traj_clearance, k_traj_chord_clearance;
+// gate_pass.hip: k_traj_gates;
 // thrust_rates.hip: k_traj_thrust_rates):
 // the LDS double buffer of the time recurrence (TcShared), its producer, the position of a
 // sample (tc_pos) and tc_walk, whose check body is a template parameter.  One definition, so

@@ -2,7 +2,9 @@
 // (gfx950): of their rows (k_traj_check) and of the chords between the rows (k_traj_sweep);
 // and the clearance of their rows (k_traj_clearance, below: the closest approach to a
 // collision OBB, where and against which), on the same walk; and the first hit of the first
-// failing chord (k_traj_first_hit, below: how far into the chord and against which OBB).
+// failing chord (k_traj_first_hit, below: how far into the chord and against which OBB); and
+// the clearance of the chords (k_traj_chord_clearance, below: the closest approach of the
+// straight chords between the rows, edge_clearance.h).
 //
 //   PathPlanner::checkTrajectoryValidity  src/PathPlanner.cpp:267-280, per track, over the rows
 //   Trajectory::evaluateRange(0, max_time, dt)  src/trajectory.cpp:81-141 would produce, with
@@ -24,6 +26,7 @@
 
 #include "clearance.h"
 #include "collision_common.h"
+#include "edge_clearance.h"
 #include "first_hit.h"
 #include "traj_sample.h"
 #include "traj_walk.h"
@@ -294,6 +297,136 @@ struct TcClear {
     }
 };
 
+// The clearance of the chords (edge_clearance.h): the minimum over a track's chords row j ->
+// row j + 1 of the squared distance between the chord and the nearest collision OBB, which
+// chord, how far into it, when, and against which OBB.  The chords are paired as TcChords pairs
+// them -- a checking lane takes G = ceil(cnt / 64) consecutive samples and the chords that END
+// at them, its first chord starting at the last sample of the lane before it (one shift per
+// coordinate), lane 0's at the previous chunk's last position, carried in a register of wave 1
+// -- and the best is kept as TcClear keeps it: nothing is ever posted, a lane's chords ascend
+// within a chunk and from chunk to chunk, so a strict < leaves it its earliest chord, and at
+// the track's end wave 1 reduces lexicographically by (d2, chord).  The chord from the
+// previous chunk needs its start row's time, which lies in the half thread 0 is overwriting:
+// wave 1 keeps each checked chunk's last time itself (ctac), so keep() has nothing to do.
+// time = t_j + t * (t_j+1 - t_j) on the time columns epp_sample_batch writes with t0 == NULL.
+// A chord with a non-finite end never updates (ClearEdge::finite).
+struct TcChordClearOut {
+    double* clearance;
+    double* t;
+    int32_t* nearest;
+};
+struct TcChordClear {
+    const double* tile;   // LDS: entries [0, n_lds)
+    const double* recs;   // the world's records
+    int n_lds, n_obb;
+    TcChordClearOut out;
+    double cx, cy, cz;    // wave 1: the previous chunk's last position
+    double ctac;          // wave 1: the previous chunk's last time
+    double bd2, bt, btime;  // wave 1: the lane's best so far
+    int64_t bchord;
+    int bobb;
+    __device__ __forceinline__ void reset() {
+        bd2 = HUGE_VAL;
+        bchord = -1;
+        bt = btime = -1.0;
+        bobb = -1;
+    }
+    __device__ __forceinline__ void begin() {
+        reset();
+        cx = cy = cz = ctac = 0.0;
+    }
+    __device__ __forceinline__ void keep(const TcShared&, int) {}
+    __device__ __forceinline__ void check(TcShared& s, int b, int cnt, int64_t base, int lane,
+                                          const double* __restrict__ coeffs, int seg0) {
+        const double otac = ctac;        // the time of the row before this chunk's first
+        ctac = s.tac[b][kRowChunk - 1];  // (a full chunk's last row; else no chunk follows)
+        const int G = (cnt + kTcCheckers - 1) / kTcCheckers;
+        const int j0 = lane * G;
+        const int j1 = min(j0 + G, cnt);
+        const bool has = j0 < cnt;
+        double l[3] = {0.0, 0.0, 0.0};  // the lane's last sample
+        if (has) tc_pos(s, b, j1 - 1, coeffs, seg0, l);
+        // (whole wave, as TcChords::check: a lane without samples hands up zeros, which only a
+        // lane without samples receives)
+        double q[3] = {__shfl_up(l[0], 1), __shfl_up(l[1], 1), __shfl_up(l[2], 1)};
+        if (lane == 0) {
+            q[0] = cx;
+            q[1] = cy;
+            q[2] = cz;
+        }
+        cx = __shfl(l[0], kTcCheckers - 1);  // (a full chunk: sample kRowChunk - 1; else unused)
+        cy = __shfl(l[1], kTcCheckers - 1);
+        cz = __shfl(l[2], kTcCheckers - 1);
+        if (!has) return;
+        for (int j = j0; j < j1; ++j) {
+            double e[3] = {l[0], l[1], l[2]};
+            if (j < j1 - 1) tc_pos(s, b, j, coeffs, seg0, e);
+            if ((base | j) != 0) {  // (row 0 ends no chord)
+                ClearEdge g;
+                g.set(q[0], q[1], q[2], e[0], e[1], e[2]);
+                double d2 = HUGE_VAL, t = -1.0;
+                int o = -1;
+                edge_min_tile(tile, 0, n_lds, g, d2, t, o);
+                edge_min_recs(recs, n_lds, n_obb, g, d2, t, o);
+                // the two rows' time columns as epp_sample_batch writes them with t0 == NULL
+                const double t0 = (j > 0 ? s.tac[b][j - 1] : otac) + 0.0, t1 = s.tac[b][j] + 0.0;
+                const bool lt = d2 < bd2;
+                bd2 = lt ? d2 : bd2;
+                bchord = lt ? base + j - 1 : bchord;
+                bt = lt ? t : bt;
+                btime = lt ? t0 + t * (t1 - t0) : btime;
+                bobb = lt ? o : bobb;
+            }
+            q[0] = e[0];
+            q[1] = e[1];
+            q[2] = e[2];
+        }
+    }
+    __device__ __forceinline__ int row(int f) const { return f; }                           // (never posted:
+    __device__ __forceinline__ double time(const TcShared&, int, int) const { return 0.0; }  //  never asked)
+    __device__ __forceinline__ void posted(const TcShared&, int, int, const double* __restrict__, int) {}
+    __device__ __forceinline__ void end(int t, int tid, bool walked, int64_t, double, int64_t* __restrict__ chord_out,
+                                        double* __restrict__ time_out) {
+        if (tid < 64) return;  // (wave-uniform: wave 1 holds the bests)
+        if (!walked) reset();  // no segment, no chord
+        for (int m = 32; m > 0; m >>= 1) {
+            const double od2 = __shfl_xor(bd2, m), ot = __shfl_xor(bt, m), otime = __shfl_xor(btime, m);
+            const long long ochord = __shfl_xor((long long)bchord, m);
+            const int oobb = __shfl_xor(bobb, m);
+            const bool take = od2 < bd2 || (od2 == bd2 && ochord < bchord);
+            bd2 = take ? od2 : bd2;
+            bchord = take ? ochord : bchord;
+            bt = take ? ot : bt;
+            btime = take ? otime : btime;
+            bobb = take ? oobb : bobb;
+        }
+        if (tid == 64) {
+            out.clearance[t] = sqrt(bd2);  // once, after the minimum
+            if (chord_out) chord_out[t] = bchord;
+            if (out.t) out.t[t] = bt;
+            if (time_out) time_out[t] = btime;
+            if (out.nearest) out.nearest[t] = bobb;
+        }
+    }
+};
+
+__global__ __launch_bounds__(kTcBlock) void k_traj_chord_clearance(WorldView w, const double* __restrict__ seg_times,
+                                                                   const double* __restrict__ coeffs,
+                                                                   const int32_t* __restrict__ wp_off, int n_tracks,
+                                                                   double dt, TcChordClearOut out,
+                                                                   int64_t* __restrict__ chord,
+                                                                   double* __restrict__ time, uint32_t stage_bytes) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    double* tile = reinterpret_cast<double*>(lds + kTcSharedBytes);
+    const double* recs = reinterpret_cast<const double*>(w.blob + w.off_aos);
+    const int n_lds = (int)(stage_bytes / (kClearDoubles * sizeof(double)));
+    clear_stage(recs, 0, n_lds, tile, kTcBlock);
+    __syncthreads();
+    TcChordClear chk{tile, recs, n_lds, w.n_obb, out};
+    chk.begin();
+    tc_walk(*reinterpret_cast<TcShared*>(lds), seg_times, coeffs, wp_off, n_tracks, dt, chord, time, chk);
+}
+
 __global__ __launch_bounds__(kTcBlock) void k_traj_clearance(WorldView w, const double* __restrict__ seg_times,
                                                              const double* __restrict__ coeffs,
                                                              const int32_t* __restrict__ wp_off, int n_tracks,
@@ -360,6 +493,15 @@ int sweep_stage(const WorldView& v, uint32_t& bytes) {
         bytes = v.front_bytes;
         return 1;
     }
+    return 0;
+}
+
+// The two clearance kernels: the first tile of entries in LDS; a larger world's remaining
+// records are read through L2.  EPP_TRAJCLEAR_STAGE=0: every record through L2 (A/B and test
+// knob)
+int clear_tile_stage(const WorldView& v, uint32_t& bytes) {
+    if (env_int("EPP_TRAJCLEAR_STAGE", 1) != 0)
+        bytes = (uint32_t)std::min(v.n_obb, kClearTile) * (uint32_t)(kClearDoubles * sizeof(double));
     return 0;
 }
 
@@ -441,15 +583,17 @@ epp_status epp_traj_clearance_batch(const epp_world* world, const double* seg_ti
                                     const int32_t* wp_offsets, int32_t n_tracks, double dt, double* clearance,
                                     int64_t* row, double* time, int32_t* nearest, void* stream) {
     static constexpr TcKernel<TcClearOut> kernels[] = {k_traj_clearance};
-    // The first tile of entries in LDS; a larger world's remaining records are read through
-    // L2.  EPP_TRAJCLEAR_STAGE=0: every record through L2 (A/B and test knob)
-    const auto stage = [](const WorldView& v, uint32_t& bytes) {
-        if (env_int("EPP_TRAJCLEAR_STAGE", 1) != 0)
-            bytes = (uint32_t)std::min(v.n_obb, kClearTile) * (uint32_t)(kClearDoubles * sizeof(double));
-        return 0;
-    };
-    return tc_launch("epp_traj_clearance_batch", n_tracks <= 0 || clearance, kernels, stage, world, seg_times, coeffs,
-                     wp_offsets, n_tracks, dt, TcClearOut{clearance, nearest}, row, time, stream);
+    return tc_launch("epp_traj_clearance_batch", n_tracks <= 0 || clearance, kernels, clear_tile_stage, world,
+                     seg_times, coeffs, wp_offsets, n_tracks, dt, TcClearOut{clearance, nearest}, row, time, stream);
+}
+
+epp_status epp_traj_chord_clearance_batch(const epp_world* world, const double* seg_times, const double* coeffs,
+                                          const int32_t* wp_offsets, int32_t n_tracks, double dt, double* clearance,
+                                          int64_t* chord, double* t, double* time, int32_t* nearest, void* stream) {
+    static constexpr TcKernel<TcChordClearOut> kernels[] = {k_traj_chord_clearance};
+    return tc_launch("epp_traj_chord_clearance_batch", n_tracks <= 0 || clearance, kernels, clear_tile_stage, world,
+                     seg_times, coeffs, wp_offsets, n_tracks, dt, TcChordClearOut{clearance, t, nearest}, chord, time,
+                     stream);
 }
 
 }  // extern "C"

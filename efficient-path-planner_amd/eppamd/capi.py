@@ -103,6 +103,8 @@ def lib() -> C.CDLL:
             "epp_traj_sweep_batch": (i32, [vp, vp, vp, vp, i32, dp, i32, vp, vp, vp]),
             "epp_states_clearance": (i32, [vp, vp, i64, vp, vp, vp]),
             "epp_traj_clearance_batch": (i32, [vp, vp, vp, vp, i32, dp, vp, vp, vp, vp, vp]),
+            "epp_motions_clearance": (i32, [vp, vp, vp, i64, vp, vp, vp, vp]),
+            "epp_traj_chord_clearance_batch": (i32, [vp, vp, vp, vp, i32, dp, vp, vp, vp, vp, vp, vp]),
             "epp_motions_first_hit": (i32, [vp, vp, vp, i64, i32, vp, vp, vp]),
             "epp_traj_first_hit_batch": (i32, [vp, vp, vp, vp, i32, dp, i32, vp, vp, vp, vp, vp]),
             "epp_gates_crossed": (i32, [vp, i32, dp, vp, vp, i64, vp, vp]),
@@ -195,7 +197,7 @@ EXPORTED = [
     "epp_traj_thrust_grid_batch", "epp_traj_scale_to_thrust_limits", "epp_generate_trajectory_flyable_host",
     "epp_traj_snap_cost", "epp_minsnap_time_gradient", "epp_minsnap_optimize_times",
     "epp_generate_trajectory_timeopt_host", "epp_minsnap_batch_constrained",
-    "epp_generate_trajectory_constrained_host",
+    "epp_generate_trajectory_constrained_host", "epp_motions_clearance", "epp_traj_chord_clearance_batch",
 ]
 
 
@@ -429,6 +431,40 @@ class World:
         sync()
         return (d_clr.download(np.float64, nt), d_row.download(np.int64, nt), d_time.download(np.float64, nt),
                 d_near.download(np.int32, nt))
+
+    def edge_clearances(self, s1: np.ndarray, s2: np.ndarray):
+        """epp_motions_clearance: per edge s1[i] -> s2[i] the Euclidean distance between the
+        segment and the nearest collision (non-filling) OBB, 0 for an edge that touches or
+        enters one, the parameter in [0, 1] at which the edge is that close and that OBB's
+        index in the world's order (the lowest index among equals); (+inf, -1.0, -1) without a
+        collision OBB or for an edge with a non-finite coordinate.  Returns (float64[n],
+        float64[n], int32[n])."""
+        s1 = np.ascontiguousarray(s1, np.float64).reshape(-1, 3)
+        s2 = np.ascontiguousarray(s2, np.float64).reshape(-1, 3)
+        n = len(s1)
+        assert len(s2) == n
+        d1, d2 = DeviceBuffer.from_array(s1), DeviceBuffer.from_array(s2)
+        d_dist, d_t, d_near = DeviceBuffer(8 * n), DeviceBuffer(8 * n), DeviceBuffer(4 * n)
+        check(lib().epp_motions_clearance(self.handle, d1.ptr, d2.ptr, n, d_dist.ptr, d_t.ptr, d_near.ptr, None))
+        sync()
+        return d_dist.download(np.float64, n), d_t.download(np.float64, n), d_near.download(np.int32, n)
+
+    def trajectory_chord_clearances(self, Ts, Cs, dt: float):
+        """epp_traj_chord_clearance_batch on the lists minsnap_batch returns: per track the
+        closest approach of the straight chords between its consecutive sampled rows
+        (Trajectory::evaluateRange at dt) to a collision OBB, the earliest chord that attains
+        it, the parameter along that chord, the track time of that point and the nearest OBB;
+        (+inf, -1, -1.0, -1.0, -1) for a track with fewer than two rows or a world without
+        collision OBBs.  Returns (float64[n], int64[n], float64[n], float64[n], int32[n])."""
+        nt = len(Ts)
+        d_T, d_C, d_off, _, _ = _upload_tracks(Ts, Cs)
+        d_clr, d_chord, d_t, d_time, d_near = (DeviceBuffer(8 * nt), DeviceBuffer(8 * nt), DeviceBuffer(8 * nt),
+                                               DeviceBuffer(8 * nt), DeviceBuffer(4 * nt))
+        check(lib().epp_traj_chord_clearance_batch(self.handle, d_T.ptr, d_C.ptr, d_off.ptr, nt, float(dt), d_clr.ptr,
+                                                   d_chord.ptr, d_t.ptr, d_time.ptr, d_near.ptr, None))
+        sync()
+        return (d_clr.download(np.float64, nt), d_chord.download(np.int64, nt), d_t.download(np.float64, nt),
+                d_time.download(np.float64, nt), d_near.download(np.int32, nt))
 
     def first_hits(self, s1: np.ndarray, s2: np.ndarray, can_pass_gate: bool = False):
         """epp_motions_first_hit: per edge s1[i] -> s2[i] the parameter in [0, 1] at which it

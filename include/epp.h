@@ -38,6 +38,10 @@
  *   epp_states_clearance / epp_traj_clearance_batch
  *       no reference counterpart: the Euclidean distance to the nearest collision OBB, per
  *       state and as the closest approach of every fitted track's rows.
+ *   epp_motions_clearance / epp_traj_chord_clearance_batch
+ *       no reference counterpart: the Euclidean distance between a straight edge and the
+ *       nearest collision OBB, per edge and as the closest approach of the chords between the
+ *       rows of every fitted track.
  *   epp_motions_first_hit / epp_traj_first_hit_batch
  *       what MotionValidator::checkMotion(s1, s2, lastValid) (src/MotionValidator.cpp:19-22, a
  *       stub there) needs: where along a straight edge World::checkRayValid first fails and
@@ -356,6 +360,66 @@ epp_status epp_states_clearance(const epp_world* w, const double* xyz, int64_t n
 epp_status epp_traj_clearance_batch(const epp_world* w, const double* seg_times, const double* coeffs,
                                     const int32_t* wp_offsets, int32_t n_tracks, double dt, double* clearance,
                                     int64_t* row, double* time, int32_t* nearest, void* stream);
+
+/* ---- swept clearance: the Euclidean distance between a straight edge and the nearest
+ * collision OBB (device pointers).  For the edge s -> e and OBB i with filling == 0, both
+ * endpoints go into the box frame by the operations of the clearance above (a from s, b from
+ * e; h the half sizes, not inflated) and d = b - a per axis.  Along the edge q(t) = a + t*d
+ * per axis, and for a local point q
+ *   F(q) = (ex*ex + ey*ey) + ez*ez,   e_k = max(|q_k| - h_k, 0)             (the d2 above)
+ *   G(q) = (wx + wy) + wz,            w_k = e_k * (q_k < 0 ? -d_k : d_k)    (half of df/dt)
+ * f(t) = F(q(t)) is convex and piecewise quadratic.  The candidates, in this order, taken into
+ * a running minimum that starts at +inf on a strict <:
+ *   1. t = 0:  f = F(a), the d2_i of the point s above, bit for bit
+ *   2. t = 1:  f = F(b), the d2_i of the point e
+ *   3. axes x, y, z, for each the face -h_k then +h_k:  t = (-+h_k - a_k) / d_k, kept iff
+ *      0 < t < 1:  f = F(q(t)).  The bracket of G's zero: (tl, gl) starts at (0, G(a)) and
+ *      (tr, gr) at (1, G(b)); a kept t with g = G(q(t)) < 0 and t > tl replaces (tl, gl), one
+ *      with g >= 0 and t < tr replaces (tr, gr)
+ *   4. iff G(a) < 0 < G(b):  t* = tl + (tr - tl) * ((-gl) / (gr - gl)),  f = F(q(t*))
+ * d2_i is the smallest f and t_i the candidate that gave it; every operation is one IEEE fp64
+ * multiply, add, subtract or divide in this association, nothing fused, every choice a select
+ * on a compare (a NaN compares false).  d2(edge) = min_i d2_i over every OBB in the order given
+ * to epp_world_create / epp_world_update on a strict <: the nearest OBB is the lowest index
+ * that attains it, t_min its t_i, and the distance is sqrt(d2), taken once after the minimum:
+ * 0 for an edge that touches or enters a box.  No grid, no AABB prefilter and no inflate
+ * radius take part.  So d2(edge) <= min(d2(s), d2(e)) of the clearance above as doubles, and a
+ * zero-length edge has exactly the distance and OBB of its point.  Against the exact minimum
+ * of f the measured error of d2 is 5.1e-16 * max(1, L^2), L the largest coordinate difference
+ * between an endpoint and the nearest box's centre.  A world without collision
+ * OBBs gives +inf, t_min -1.0 and OBB -1, and so does an edge with a coordinate that is not
+ * finite, which takes part in no minimum.
+ *
+ * epp_motions_clearance: dist[i] (n, device f64), t_min[i] (n, device f64, may be NULL) and
+ * nearest[i] (n, device int32, may be NULL) for each of the n edges s1[i] -> s2[i] (n x 3 f64
+ * each).  Stream-ordered, no host synchronisation and no allocation; a stale world index is
+ * rebuilt first, as by epp_states_clearance, so the call can be captured (epp_graph_begin)
+ * after epp_world_build_index.  EPP_ERR_INVALID_ARGUMENT (before any device work) for a NULL
+ * world, n < 0, or a NULL s1, s2 or dist with n > 0; n == 0 launches nothing. */
+epp_status epp_motions_clearance(const epp_world* w, const double* s1, const double* s2, int64_t n, double* dist,
+                                 double* t_min, int32_t* nearest, void* stream);
+/* The closest approach of the chords of every track of a batch in the layout of
+ * epp_minsnap_batch, straight from the coefficients, in one launch and without writing a row.
+ * Over the chords row j -> row j + 1 of the rows of Trajectory::evaluateRange(0, max_time, dt)
+ * of track k: clearance[k] (n_tracks, device f64) is the square root of the minimum d2;
+ * chord[k] (device int64, may be NULL) the earliest j that attains it; t[k] (device f64, may be
+ * NULL) that chord's t_min; time[k] (device f64, may be NULL) = t_j + t * (t_j+1 - t_j) on the
+ * time columns epp_sample_batch writes with t0 == NULL: one subtract, one multiply, one add,
+ * unfused; nearest[k] (device int32, may be NULL) that chord's nearest OBB.  A track with
+ * fewer than two rows (one waypoint, the NaN times of a failed fit) or a world without
+ * collision OBBs gives +inf, -1, -1.0, -1.0, -1; a chord with a non-finite end is ignored.
+ * The answers are those of epp_sample_count + epp_sample_batch + epp_motions_clearance(s1 =
+ * rows j, s2 = rows j + 1, columns 0 / 3 / 6) followed by a per-track minimum that prefers the
+ * earliest chord, bit for bit (the same recurrence, Horner steps and d2, one square root after
+ * an exact minimum).  So clearance[k] <= epp_traj_clearance_batch's for every track with two
+ * rows or more.  Stream-ordered, no host synchronisation and no allocation; a stale world
+ * index is rebuilt first, so the call can be captured (epp_graph_begin) after
+ * epp_world_build_index.  EPP_ERR_INVALID_ARGUMENT (before any device work) for a NULL world,
+ * n_tracks < 0, dt <= 0 or not finite, or a NULL seg_times, coeffs, wp_offsets or clearance
+ * with n_tracks > 0; n_tracks == 0 launches nothing. */
+epp_status epp_traj_chord_clearance_batch(const epp_world* w, const double* seg_times, const double* coeffs,
+                                          const int32_t* wp_offsets, int32_t n_tracks, double dt, double* clearance,
+                                          int64_t* chord, double* t, double* time, int32_t* nearest, void* stream);
 
 /* ---- first hit: where a straight edge is first blocked, and by which OBB (device pointers)
  * For the edge s -> e, can_pass_gate and OBB i with owner radius r (r_gate for a gate's OBB,

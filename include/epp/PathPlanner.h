@@ -142,6 +142,30 @@ public:
     void candidateClearances(const std::vector<std::vector<Vec3>>& waypointSets, double v_max, double a_max, double dt,
                              std::vector<double>& clearance, std::vector<long>* row = nullptr,
                              std::vector<double>* time = nullptr, std::vector<int>* nearest = nullptr) const;
+    // candidateClearances of the chords instead of the rows (an addition of this build): a
+    // track that passes a bar between two rows keeps the margin of neither row.  The fit of
+    // every set as above and, on the same stream with one synchronisation,
+    // epp_traj_chord_clearance_batch (include/epp.h) of the straight chords between the fits'
+    // consecutive rows at dt.  clearance[k]: the smallest Euclidean distance between a chord
+    // of set k and a collision (non-filling) OBB, 0 for a chord that touches or enters one,
+    // +inf for a world without any (never more than candidateClearances' for a track of two
+    // rows or more); chord / t / time / nearest (optional): the earliest chord row j -> row
+    // j + 1 that attains it, the parameter in [0, 1] along it, the track time of that point
+    // and the nearest OBB's index in the world's order (the lowest among equals); -1, -1.0,
+    // -1.0, -1 when the clearance is +inf.  Throws as checkCandidateTrajectories.
+    void candidateSweptClearances(const std::vector<std::vector<Vec3>>& waypointSets, double v_max, double a_max,
+                                  double dt, std::vector<double>& clearance, std::vector<long>* chord = nullptr,
+                                  std::vector<double>* t = nullptr, std::vector<double>* time = nullptr,
+                                  std::vector<int>* nearest = nullptr) const;
+    // How much room a waypoint polyline (planPath's result, a shortcut path, includeGates2's)
+    // leaves (an addition of this build): the smallest Euclidean distance between one of its
+    // edges path[j] -> path[j + 1] and a collision (non-filling) OBB, in one
+    // World::edgeClearances call over the edges; edge / t / nearest (optional): the earliest
+    // edge that attains it, the parameter in [0, 1] along it and the OBB's index in the world's
+    // order; +inf, -1, -1.0, -1 without a collision OBB.  Throws std::invalid_argument for a
+    // path of fewer than two points.
+    double pathClearance(const std::vector<Vec3>& path, long* edge = nullptr, double* t = nullptr,
+                         int* nearest = nullptr) const;
     // Where and against what each of K candidate waypoint sets' trajectories first fails the
     // swept check (an addition of this build): the fit of every set as above and, on the same
     // stream with one synchronisation, epp_traj_first_hit_batch (include/epp.h) of the fits'

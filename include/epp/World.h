@@ -64,6 +64,14 @@ public:
     // lastValid) needs.
     void firstHits(const double* s1, const double* s2, int64_t n, bool canPassGate, double* t,
                    int32_t* obb = nullptr) const;
+    // Swept clearance (an addition of this build; epp_motions_clearance, include/epp.h): dist[i]
+    // is the Euclidean distance between the edge s1[i] -> s2[i] and the nearest collision
+    // (non-filling) OBB, 0 for an edge that touches or enters one; t[i] (optional) the
+    // parameter in [0, 1] at which the edge is that close; nearest[i] (optional) that OBB's
+    // index in obbs(), the lowest among equals.  +inf / -1.0 / -1 without a collision OBB (an
+    // empty world included) or for an edge with a non-finite coordinate.
+    void edgeClearances(const double* s1, const double* s2, int64_t n, double* dist, double* t = nullptr,
+                        int32_t* nearest = nullptr) const;
 
     // Device handle (rebuilt lazily after mutations); nullptr for an empty world.
     const epp_world* device() const;
